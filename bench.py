@@ -10,9 +10,14 @@ collective => weak scaling) and, beside it, C4's 200 epochs sharded over the ran
 of the shared block (strong scaling, reported under config.sharded_joint_fit).
 Inputs are resident in HBM before the timed region; the Moffat stage and noise propagation are one-time setup.
 
+A plain run measures the headline only: set-up, `--warmup` steps, `--steps` timed steps, the outputs of the last step
+(`--dump-outputs DIR`) and the result line.  `--full` adds everything else the line can carry: the rocprofv3 counter
+traffic, the measured copy bandwidth, the C4 / C4-shard / C5-shard / C3-shard / field-distortion / star-photometry
+entries, the CPU baselines and, for N > 1, the sharded fits.
+
 `--gpus N` without a launcher (WORLD_SIZE unset) starts N rank processes itself before anything touches the GPU.
-For N > 1 every rank process is a supervisor that stays off the GPU and runs the measurement in a child (supervise_rank):
-the headline line exists before the sharded joint fits start and survives whatever happens in them.
+With --full and N > 1 every rank process is a supervisor that stays off the GPU and runs the measurement in a child
+(supervise_rank): the headline line exists before the sharded joint fits start and survives whatever happens in them.
 """
 import argparse
 import csv
@@ -361,6 +366,26 @@ def psf_step(b, stars0, ab):
     b.set_grid(None)
     b.set_stars(stars0)
     b.run_adabelief(ITERS_PER_STEP, **ab)
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: writes every array of `outputs` (indexed by frame first) as path/<name>.npy, in the dtype it was
+    computed in.  Past DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of frames is written for every array, and the
+    sampled frame indices as frames.npy."""
+    os.makedirs(path, exist_ok=True)
+    F = next(iter(outputs.values())).shape[0]
+    per_frame = sum(a.nbytes for a in outputs.values()) / F
+    headers = 128 * (len(outputs) + 1)      # an .npy header is 128 bytes for arrays of these few dimensions
+    keep = min(F, int((DUMP_LIMIT_BYTES - headers - 8 * F) // per_frame))
+    if keep < F:
+        frames = np.sort(np.random.default_rng(0).choice(F, keep, replace=False))
+        outputs = {k: a[frames] for k, a in outputs.items()}
+        outputs['frames'] = frames.astype(np.float64)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def effective_cpus():
@@ -842,6 +867,11 @@ def main():
     ap.add_argument('--steps', type=int, default=50)   # 50 steps of ~40 ms: a timed region of about two seconds
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--config', default='C2', choices=['C1', 'C2', 'C3'])
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the last timed step computed (rank 0's batch) as DIR/<name>.npy, 64 MB at most")
+    ap.add_argument('--full', action='store_true',
+                    help='also the counter traffic, the copy bandwidth, the other workloads, the CPU baselines and, for N > 1, '
+                         'the sharded fits (the --no-* options below leave parts of these out)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra', '--no-joint', dest='no_extra', action='store_true',
                     help='skip the C4 / C5-shard / C3-shard entries')
@@ -850,13 +880,16 @@ def main():
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--pmc-child-sections', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.pmc_child_sections:
         pmc_sections_child()
         return
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
-    if args.gpus > 1 and os.environ.get('LCMI_BENCH_WORKER') != '1' and not args.no_sharded_joint:
+    sharded_fits = args.full and not args.no_sharded_joint
+    if args.gpus > 1 and os.environ.get('LCMI_BENCH_WORKER') != '1' and sharded_fits:
         sys.exit(supervise_rank(sys.argv[1:]))
 
     # stdout carries ONE line, the JSON of rank 0: libraries that chat on file descriptor 1 (gloo's "[Gloo] Rank 0 is connected
@@ -872,9 +905,9 @@ def main():
         print(f'bench.py: --gpus {args.gpus} but WORLD_SIZE={world}', file=sys.stderr)
         sys.exit(2)
 
-    traffic, traffic_source = None, 'not measured (--no-traffic, N > 1 or a profiler child)'
+    traffic, traffic_source = None, 'not measured (without --full, --no-traffic, N > 1 or a profiler child)'
     joint_traffic = {}
-    if world == 1 and not args.no_traffic and not args.pmc_child and args.config == 'C2':
+    if args.full and world == 1 and not args.no_traffic and not args.pmc_child and args.config == 'C2':
         traffic, traffic_source = measure_traffic()   # before this process touches the GPU
         if not args.no_extra:
             joint_traffic = measure_section_traffic()
@@ -926,6 +959,8 @@ def main():
     hist = b.loss_history()
     finite = bool(np.all(np.isfinite(hist)))
     res = b.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(res, stars=b.get_stars(), grid=b.get_grid(), loss_history=hist))
 
     if rank == 0:
         value = F * S * world * ITERS_PER_STEP * args.steps / elapsed
@@ -958,15 +993,16 @@ def main():
                        'median_reduced_chi2': float(np.median(res['chi2']))},
             'roofline': roof,
         }
-        try:  # the box's own copy bandwidth beside the 8 TB/s specification
-            import ctypes
-            g = ctypes.c_float()
-            ctx.check(_lib.lib().lc_copy_bandwidth(ctx.h, 1 << 30, 10, ctypes.byref(g)), 'lc_copy_bandwidth')
-            out['roofline']['measured_copy_GBps'] = g.value
-            out['roofline']['frac_of_measured_copy'] = roof['achieved'] / g.value
-        except Exception:
-            out['roofline']['measured_copy_GBps'] = None
-        if world == 1 and not args.no_extra:
+        if args.full:
+            try:  # the box's own copy bandwidth beside the 8 TB/s specification
+                import ctypes
+                g = ctypes.c_float()
+                ctx.check(_lib.lib().lc_copy_bandwidth(ctx.h, 1 << 30, 10, ctypes.byref(g)), 'lc_copy_bandwidth')
+                out['roofline']['measured_copy_GBps'] = g.value
+                out['roofline']['frac_of_measured_copy'] = roof['achieved'] / g.value
+            except Exception:
+                out['roofline']['measured_copy_GBps'] = None
+        if args.full and world == 1 and not args.no_extra:
             extra = []
             for fn, kw in ((joint_workload, dict(E=200, n=64, M=2, seed=104, iters=2000, label='C4')),
                            (joint_workload, dict(E=25, n=64, M=2, seed=104, iters=2000,
@@ -997,7 +1033,7 @@ def main():
                     except Exception as e:
                         extra[idx]['cpu_baseline'] = {'value': None, 'error': repr(e)}
             out['config']['other_workloads'] = extra
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out['cpu_baseline'] = cpu_baseline(ds, weight, b, stars0, ss)
             except Exception as e:  # the bench line must still be printed
@@ -1013,7 +1049,7 @@ def main():
         os.write(real_stdout, b'HEADLINE_DONE\n')
 
     sharded = sharded_peer = sharded_c5 = sharded_c5_rccl = sharded_c3 = None
-    if world > 1 and not args.no_sharded_joint:
+    if world > 1 and sharded_fits:
         try:   # C3 as north_star splits it: the 500 frames over the ranks, no collective
             sharded_c3 = c3_sharded_fit(ctx, rank, world, dist)
         except Exception as e:

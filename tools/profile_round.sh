@@ -9,8 +9,8 @@ DST=$REPO/gpurun_out/profiles_$LABEL
 mkdir -p $OUT $DST
 export TMPDIR=/tmp
 cd /tmp
-# the bench command itself (fewer steps; the timed kernel and its launch shape are the same)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $REPO/bench.py --steps 5 --warmup 1 --no-traffic --no-cpu-baseline > $OUT/bench.log 2>&1
+# the bench command itself with its other workloads (--full; fewer steps; the timed kernel and its launch shape are the same)
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $REPO/bench.py --full --steps 5 --warmup 1 --no-traffic --no-cpu-baseline > $OUT/bench.log 2>&1
 echo "bench trace done"
 LCMI_PTS=0.01 LCMI_FU=10 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c4 -- python3 $REPO/tools/joint_speed.py 200 64 2 300 > $OUT/c4.log 2>&1
 echo "c4 trace done"

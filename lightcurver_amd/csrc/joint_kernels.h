@@ -1542,10 +1542,14 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
       if (kx == N - 1) { ulo -= mext; uhi += mext; }
       if (ky == 0) { vlo -= mext; vhi += mext; }
       if (ky == N - 1) { vlo -= mext; vhi += mext; }
-      if (kx == 0) vlo = 0;
-      if (kx == N - 1) vhi = N - 1;
-      if (ky == 0) ulo = 0;
-      if (ky == N - 1) uhi = N - 1;
+      // the samples clamped onto a border line of h form a strip that leaves (px, py) along the rotated axis: toward scene
+      // column 0 / row 0 while cos(alpha) >= 0, toward column / row N - 1 past 90 degrees (a pier flip: 180).  Near 90 degrees
+      // the strip is no wider than the 4 x 4 window either way.
+      const bool fwd = (ca >= 0.f);
+      if (kx == 0) { if (fwd) vlo = 0; else vhi = N - 1; }
+      if (kx == N - 1) { if (fwd) vhi = N - 1; else vlo = 0; }
+      if (ky == 0) { if (fwd) ulo = 0; else uhi = N - 1; }
+      if (ky == N - 1) { if (fwd) uhi = N - 1; else ulo = 0; }
       if (translated) {
         // exact candidate ranges: scene pixel (u, v) touches rows clamp(u + iyc), clamp(u + iyc + 1) and the same in x
         ulo = (ky == 0) ? 0 : ky - iyc - 1;

@@ -94,10 +94,14 @@ def make_psf_dataset(F, S, n, ss=2, seed=0, rms=5.0, masked_fraction=0.01, dtype
 
 
 def make_roi_dataset(E, M, n, ss=2, seed=0, rms=5.0, with_background=True, shift_sigma=0.3,
-                     alpha_sigma=0.0, dtype=np.float32):
+                     alpha_sigma=0.0, dtype=np.float32, alpha=None, dx=None, dy=None):
     """E epochs of an n x n ROI with M point sources, a smooth background and one narrow PSF per
     epoch.  Returns data, noisemap (E,n,n), psf (E,N,N), truth parameters (STARRED kwargs layout:
-    a epoch-major, c_x, c_y, dx, dy, alpha, h flat, mean)."""
+    a epoch-major, c_x, c_y, dx, dy, alpha, h flat, mean).
+
+    alpha, dx, dy: optional explicit rotation per epoch in degrees (a pier flip, an alt-az field) and shift
+    per epoch in data pixels (length E each).  They replace the drawn values and consume no random draws:
+    every other value is what the same seed gives without them (the draws still happen and are discarded)."""
     rng = np.random.default_rng(seed)
     N = ss * n
     c0 = (N - 1) / 2.0
@@ -107,11 +111,20 @@ def make_roi_dataset(E, M, n, ss=2, seed=0, rms=5.0, with_background=True, shift
     phase = rng.uniform(0, 2 * math.pi, size=M)
     e = np.arange(E)
     a = base[None, :] * (1.0 + 0.1 * np.sin(2 * math.pi * e[:, None] / max(E, 1) + phase[None, :]))
-    dx = rng.normal(0.0, shift_sigma, size=E)
-    dy = rng.normal(0.0, shift_sigma, size=E)
-    dx[0] = dy[0] = 0.0
-    alpha = rng.normal(0.0, alpha_sigma, size=E) if alpha_sigma > 0 else np.zeros(E)
-    alpha[0] = 0.0
+    dx_drawn = rng.normal(0.0, shift_sigma, size=E)
+    dy_drawn = rng.normal(0.0, shift_sigma, size=E)
+    dx_drawn[0] = dy_drawn[0] = 0.0
+    alpha_drawn = rng.normal(0.0, alpha_sigma, size=E) if alpha_sigma > 0 else np.zeros(E)
+    alpha_drawn[0] = 0.0
+
+    def _given(v, drawn, name):
+        if v is None:
+            return drawn
+        v = np.array(v, dtype=np.float64).reshape(-1)
+        if v.shape != (E,):
+            raise ValueError(f'{name} must hold one value per epoch ({E}), got {v.shape}')
+        return v
+    dx, dy, alpha = _given(dx, dx_drawn, 'dx'), _given(dy, dy_drawn, 'dy'), _given(alpha, alpha_drawn, 'alpha')
     h = np.zeros((N, N))
     if with_background:
         u = np.arange(N, dtype=np.float64)

@@ -15,8 +15,8 @@ FREE = ['a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h']
 LOSS = dict(lam_scales=1.0, lam_hf=1.5, lam_positivity=20.0, lam_positivity_ps=3.0, lam_pts_source=0.3, lam_flux_uniformity=0.7)
 
 
-def _problem(E, M, n, seed, rotate):
-    ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=seed)
+def _problem(E, M, n, seed, rotate, alpha=None):
+    ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=seed, alpha=alpha)
     p = {k: np.asarray(v, np.float64) for k, v in ds['truth'].items()}
     rng = np.random.default_rng(seed)
     p['a'] = p['a'] * rng.uniform(0.8, 1.2, p['a'].shape)
@@ -26,6 +26,8 @@ def _problem(E, M, n, seed, rotate):
     p['dy'] = p['dy'] + rng.uniform(-0.3, 0.3, E)
     p['mean'] = rng.uniform(-1e-3, 1e-3, E)
     p['alpha'] = rng.uniform(-4.0, 4.0, E) if rotate else np.zeros(E)
+    if alpha is not None:
+        p['alpha'] = np.array(alpha, dtype=np.float64)
     p['h'] = p['h'] + 2e-3 * rng.standard_normal(p['h'].shape)   # some negative pixels: the positivity term of h is active
     return ds, p
 
@@ -40,7 +42,23 @@ def _oracle_fn(ds, sig2, W):
 
 @pytest.mark.parametrize('E,M,n,rotate,with_W', [(3, 2, 16, False, False), (2, 1, 16, True, True), (3, 3, 24, True, True)])
 def test_loss_gradient_and_model_equal_the_oracle(E, M, n, rotate, with_W):
-    ds, p = _problem(E, M, n, 50 + n + E, rotate)
+    _check_against_the_oracle(*_problem(E, M, n, 50 + n + E, rotate), M, n, with_W)
+
+
+# (alpha of epochs 1.., shift (ss dx, ss dy) of epochs 1.. in high-resolution pixels): past 90 degrees, where the samples
+# clamped onto a border line of h run toward the far side of the scene, with shifts of one to three data pixels
+@pytest.mark.parametrize('n,alpha,shift', [(16, 90.0, (-2.6, 3.4)), (16, 120.0, (2.6, -0.3)), (16, 180.0, (-5.3, -4.7)),
+                                           (24, -135.0, (5.3, 2.6)), (24, 180.0, (-2.6, 3.4))])
+def test_loss_gradient_and_model_equal_the_oracle_at_large_angles(n, alpha, shift):
+    E, M = 3, 2
+    ds, p = _problem(E, M, n, 70 + n, False, alpha=[0.0, alpha, 0.5 * alpha])
+    sx, sy = shift
+    p['dx'] = np.array([0.0, sx, -0.5 * sy]) / 2.0
+    p['dy'] = np.array([0.0, sy, 0.5 * sx]) / 2.0
+    _check_against_the_oracle(ds, p, M, n, True)
+
+
+def _check_against_the_oracle(ds, p, M, n, with_W):
     sig2 = ds['noisemap'].astype(np.float64) ** 2
     N = 2 * n
     W = None
@@ -56,6 +74,11 @@ def test_loss_gradient_and_model_equal_the_oracle(E, M, n, rotate, with_W):
     for k in FREE:
         gk = go[k].numpy()
         assert np.abs(g[k] - gk).max() / np.abs(gk).max() < 1e-9, k
+    # the two-pixel border ring of h, where the clamped samples land, relative to its own largest element
+    ring = np.ones((N, N), bool)
+    ring[2:-2, 2:-2] = False
+    gr, gor = g['h'].reshape(N, N)[ring], go['h'].numpy().reshape(N, N)[ring]
+    assert np.abs(gr - gor).max() / np.abs(gor).max() < 1e-9
     mo = om.deconv_model(po, om.T(ds['psf']), 2, n).numpy()
     assert np.abs(model - mo).max() / np.abs(mo).max() < 1e-12
     c.close()
@@ -96,3 +119,28 @@ def test_float32_build_tracks_the_float64_one():
         out.append(c.run(10, lr0=1e-4, free=FREE, threads=2))
         c.close()
     assert np.all(np.isfinite(out[1])) and np.abs(out[1] - out[0]).max() / abs(out[0][0]) < 1e-4
+
+
+def test_explicit_alpha_consumes_no_random_draws():
+    """make_roi_dataset(alpha=..., dx=..., dy=...) replaces the angles / shifts only: the same seed gives the same fluxes, positions, shifts and PSFs,
+    and alpha=None / all zeros is the default dataset bit for bit (tests/golden/ depends on it)."""
+    E, M, n = 3, 2, 16
+    a = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=5)
+    b = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=5, alpha=np.zeros(E))
+    c = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=5, alpha=[0.0, 180.0, 120.0])
+    for k in ('data', 'noisemap', 'psf'):
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a['psf'], c['psf'])
+    for k in ('a', 'c_x', 'c_y', 'dx', 'dy', 'h'):
+        assert np.array_equal(a['truth'][k], c['truth'][k]), k
+    assert np.array_equal(c['truth']['alpha'], [0.0, 180.0, 120.0])
+    assert np.array_equal(a['data'][0], c['data'][0]) and not np.allclose(a['data'][1], c['data'][1])
+    d = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=5, alpha_sigma=2.0)
+    t = d['truth']
+    e = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=5, alpha_sigma=2.0, alpha=t['alpha'], dx=t['dx'], dy=t['dy'])
+    assert np.array_equal(d['data'], e['data']) and np.array_equal(d['psf'], e['psf'])
+    f = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=5, dx=[0.0, 1.3, -2.65], dy=[0.0, -0.2, 1.7])
+    assert np.array_equal(a['psf'], f['psf']) and np.array_equal(f['truth']['dy'], [0.0, -0.2, 1.7])
+    assert np.array_equal(a['truth']['h'], f['truth']['h']) and np.array_equal(a['truth']['a'], f['truth']['a'])
+    with pytest.raises(ValueError):
+        make_roi_dataset(E=E, M=M, n=n, ss=2, seed=5, alpha=[0.0, 1.0])

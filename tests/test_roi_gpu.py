@@ -10,15 +10,32 @@ pytestmark = pytest.mark.gpu
 
 
 def test_two_stage_roi_fit_recovers_light_curves():
+    E = 24
+    _two_stage_fit(E, np.zeros(E))
+
+
+def test_two_stage_roi_fit_across_a_pier_flip():
+    """A German-mount pier flip: half the frames rotated by 180 degrees (+- 0.5 from plate solving), epoch 0 at 0.  The
+    same recipe and the same acceptance as the unrotated fit."""
+    E = 24
+    rng = np.random.default_rng(3)
+    angles = rng.uniform(-0.5, 0.5, E)
+    angles[0] = 0.0
+    angles[1::2] += 180.0
+    _two_stage_fit(E, angles)
+
+
+def _two_stage_fit(E, angles):
     from lightcurver_amd.processes.roi_modelling import fluxes_from_model, model_roi_cutouts
-    E, M, n, ss = 24, 2, 32, 2
-    ds = make_roi_dataset(E=E, M=M, n=n, ss=ss, seed=77)
+    M, n, ss = 2, 32, 2
+    # (angles all zero: the dataset every earlier version of this test drew)
+    ds = make_roi_dataset(E=E, M=M, n=n, ss=ss, seed=77, alpha=angles)
     t = ds['truth']
     off = (n - 1) / 2.0
     rng = np.random.default_rng(0)
     out = model_roi_cutouts(ds['data'] * ds['scale'], ds['noisemap'] * ds['scale'], ds['psf'], ss,
                             t['c_x'] + off + rng.normal(0, 0.3, M), t['c_y'] + off + rng.normal(0, 0.3, M),
-                            angles_to_north=np.zeros(E), fix_point_source_astrometry=2.0,
+                            angles_to_north=angles, fix_point_source_astrometry=2.0,
                             regularization={'regularization_scatter_fluxes_pre_optim': 1.0,
                                             'regularization_scatter_fluxes_main_optim': 0.0},
                             roi_deconv_translations_iters=300, roi_deconv_all_iters=1500)

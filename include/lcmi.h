@@ -261,6 +261,19 @@ int lc_joint_param_history_end(lc_joint *j);
 int lc_joint_create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss, const float *data,
                            const float *sigma2, const float *psf, lc_joint **out);
 int lc_joint_get_group_loss_history(lc_joint *j, float *history /* [G][count_per_group] */, int count_per_group);
+/* ... with a background grid per star (the reference's do_one_star_forward_modelling with starlet_global_background=True,
+ * its own default: star_photometry.py:23-24, and the pipeline's switch for crowded fields).  Same arguments and the same
+ * object as lc_joint_create_groups, plus every star's own background: block h has G * N * N entries, star-major
+ * (set/get_param, set_free); lc_joint_set_loss takes W as [G][J][N][N]; lc_joint_propagate_noise writes [G][J + 1][N][N]
+ * (each star's levels from its own epochs); model, fisher_flux_sigma and deconvolved use each epoch's own star's h.
+ * lc_joint_run_adabelief needs h free with the starlet / positivity regulariser on (LC_ERR_UNSUPPORTED otherwise).  Each
+ * star's trajectory is bit for bit that of lc_joint_create + lc_joint_run_adabelief on that star alone with h free.  No
+ * point-source starlet term or prior; loss_grad, the step / sharded entry points, L-BFGS and the parameter history return
+ * LC_ERR_UNSUPPORTED.  Stamp sizes with a single-workgroup update only (n = 16, 24, 32 at ss = 2, n = 16 at ss = 1);
+ * LC_ERR_UNSUPPORTED at create otherwise; lc_joint_groups_background_supported(n, ss) answers (1 / 0) without a device. */
+int lc_joint_groups_background_supported(int n, int ss);
+int lc_joint_create_groups_background(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss,
+                                      const float *data, const float *sigma2, const float *psf, lc_joint **out);
 /* FisherCovariance(diagonal_only=True) with only `a` free -> sigma(a) [E*M]
  * (lightcurver/utilities/starred_utilities.py:36-38). */
 int lc_joint_fisher_flux_sigma(lc_joint *j, float *sigma_a);

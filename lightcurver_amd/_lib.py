@@ -85,9 +85,11 @@ SIGNATURES = {
     'lc_batched_lbfgs': (C.c_int, [C.c_int, C.c_int, dp, dp, dp, C.c_int, LBFGS_EVAL, vp, dp, C.POINTER(C.c_int)]),
     'lc_apply_distortion': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, fp, fp]),
     'lc_joint_supported': (C.c_int, [C.c_int, C.c_int]),
+    'lc_joint_groups_background_supported': (C.c_int, [C.c_int, C.c_int]),
     'lc_joint_set_debug_global': (C.c_int, [C.c_int]),
     'lc_joint_create': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]),
     'lc_joint_create_groups': (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]),
+    'lc_joint_create_groups_background': (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]),
     'lc_joint_get_group_loss_history': (C.c_int, [vp, fp, C.c_int]),
     'lc_joint_destroy': (None, [vp]),
     'lc_joint_set_param': (C.c_int, [vp, C.c_int, fp, C.c_int]),

@@ -23,6 +23,7 @@
 using namespace lc;
 
 constexpr int kMaxParts = 16;  // workgroups per epoch of the phased launches
+constexpr int kRegsStride = 4 + 3 * kMaxSources + 4;  // floats of lc_joint::regs (per star of a batch with backgrounds)
 typedef void (*epoch_fn)(JointArgs);
 typedef void (*update_fn)(JointUpdArgs);
 struct JointVariant {
@@ -44,6 +45,10 @@ struct JointVariant {
   // a build of its own beside an LDS-spectrum kernel (same N, SS, L: same spectra)
   epoch_fn ek_cluster = nullptr;
   int cl_lds = 0, cl_thr = 0, cl_lpf = 16;
+  // batched star photometry with a background grid per star (lc_joint_create_groups_background): the epoch kernel that reads
+  // its epoch's star (JointArgs::group) and the single-workgroup update over the stars' views
+  epoch_fn ek_grp = nullptr;
+  void (*uk_grp)(const JointUpdArgs *) = nullptr;
 };
 
 typedef void (*mreg_fn)(MregArgs);
@@ -144,6 +149,11 @@ struct lc_joint {
   int G = 0;
   std::vector<int> gstart;
   int *group_dev = nullptr;
+  // ... with a background grid per star (lc_joint_create_groups_background): h, W, qscr, greg, regs and the reduced block
+  // per star (strides N^2, (J + 1) N^2, N^2, kRegsStride, NN + 4 M + 2); views_dev then holds three sets of G views - the
+  // fused reduction + update, the regulariser launch, the final-loss / reduction launches
+  bool bg = false;
+  int *gstart_dev = nullptr;
   JointUpdArgs *views_dev = nullptr;
   float *ghist = nullptr, *shared_g = nullptr, *a_ref_g = nullptr, *out_loss_g = nullptr;
   int ghist_cap = 0;
@@ -186,16 +196,23 @@ int d2h(lc_joint *j, void *dst, const void *src, size_t bytes) {
   return LC_OK;
 }
 
-template <int N, int SS, int L, int PX, int NW, int LPF = 16>
+// BG: also the per-star background forms (lc_joint_create_groups_background) - the sizes of its scope, n <= 32
+template <int N, int SS, int L, int PX, int NW, int LPF = 16, bool BG = true>
 JointVariant make_jv() {
   typedef JointCfg<N, SS, L, NW, false, LPF> C;
-  return JointVariant{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, joint_update_kernel<N, PX>, N * N / PX,
-                      (int)(StarletLds<N>::FLOATS * sizeof(float)), false, joint_epoch_kernel<C, true>};
+  JointVariant v{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, joint_update_kernel<N, PX>, N * N / PX,
+                 (int)(StarletLds<N>::FLOATS * sizeof(float)), false, joint_epoch_kernel<C, true>};
+  if constexpr (BG) {
+    v.ek_grp = joint_epoch_kernel<C, false, 0, true>;
+    v.uk_grp = joint_update_groups_uk_kernel<N, PX>;
+  }
+  return v;
 }
 // ... with the cluster form beside it: four-wave workgroups (one wave per SIMD), spectrum in the global scratch
 template <int N, int SS, int L, int PX, int NW, int LPF, int CNW, int CLPF>
 JointVariant make_jv_cl() {
-  JointVariant v = make_jv<N, SS, L, PX, NW, LPF>();
+  // (no per-star background form: n = 64 is outside its scope - the one-star fit runs the cluster form there)
+  JointVariant v = make_jv<N, SS, L, PX, NW, LPF, false>();
   typedef JointCfg<N, SS, L, CNW, true, CLPF> CC;
   v.ek_cluster = joint_epoch_kernel<CC, false, 7>;
   v.cl_lds = CC::LDS_BYTES;
@@ -461,7 +478,14 @@ int launch_epochs(lc_joint *j, int mode, int isrc, bool want_hgrad, float *model
       return 0;
     }
   }
-  if (j->G > 0) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry runs the point-source-only kernel (LCMI_JOINT_FFT_ONLY is set?)");
+  if (j->G > 0 && !j->bg) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry runs the point-source-only kernel (LCMI_JOINT_FFT_ONLY is set?)");
+  if (j->bg) {  // one workgroup per epoch of [e0, e1), each with its star's h and positions (dynamic LDS set at create)
+    if (e1 < 0) e1 = j->E;
+    A.e_off = e0;
+    hipLaunchKernelGGL(v->ek_grp, dim3(e1 - e0), dim3(v->e_thr), v->e_lds, ps_stream ? ps_stream : j->ctx->stream, A);
+    LC_HIP(j->ctx, hipGetLastError());
+    return A.need_hgrad;
+  }
   // global-spectrum kernels: with many workgroups in flight the 8 / 16-byte column accesses saturate L2 / Infinity Cache and
   // the LDS-tile variant of the column passes wins (128 x 128 ROIs: 32 epochs +1.4 %, 64 +-0, 125 -1 %, 160 -7 %, 200 -16 %,
   // 1000 -15 %; LCMI_TILE_COLS=0/1 overrides the choice)
@@ -1211,19 +1235,33 @@ int launch_aux(lc_joint *j, int mode, const float *scene, const float2 *St_in, f
 extern "C" {
 
 int lc_joint_supported(int n, int ss) { return find_jv(n, ss) != nullptr; }
+int lc_joint_groups_background_supported(int n, int ss) {
+  const JointVariant *v = find_jv(n, ss);
+  return (v && v->uk_grp) ? 1 : 0;
+}
 int lc_joint_set_debug_global(int on) {
   g_debug_global = on ? 1 : 0;
   return LC_OK;
 }
 
 static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const float *data, const float *sigma2,
-                             const float *psf, int G, const int32_t *epochs_per_group, lc_joint **out);
+                             const float *psf, int G, const int32_t *epochs_per_group, lc_joint **out, bool background = false);
+static int create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss, const float *data,
+                         const float *sigma2, const float *psf, lc_joint **out, bool background);
 int lc_joint_create(lc_ctx *ctx, int E, int M, int n, int ss, const float *data, const float *sigma2,
                     const float *psf, lc_joint **out) {
   return joint_create_impl(ctx, E, M, n, ss, data, sigma2, psf, 0, nullptr, out);
 }
 int lc_joint_create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss, const float *data,
                            const float *sigma2, const float *psf, lc_joint **out) {
+  return create_groups(ctx, G, epochs_per_group, M, n, ss, data, sigma2, psf, out, false);
+}
+int lc_joint_create_groups_background(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss,
+                                      const float *data, const float *sigma2, const float *psf, lc_joint **out) {
+  return create_groups(ctx, G, epochs_per_group, M, n, ss, data, sigma2, psf, out, true);
+}
+static int create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss, const float *data,
+                         const float *sigma2, const float *psf, lc_joint **out, bool background) {
   if (!ctx || G <= 0 || !epochs_per_group) {
     if (ctx) ctx->err = "lc_joint_create_groups: invalid argument";
     return LC_ERR_INVALID;
@@ -1235,16 +1273,23 @@ int lc_joint_create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, 
   }
   if (E > (1 << 24)) LC_FAIL(ctx, LC_ERR_INVALID, "lc_joint_create_groups: too many epochs");
   if (M <= 0) LC_FAIL(ctx, LC_ERR_INVALID, "lc_joint_create_groups: at least one point source per star");
-  return joint_create_impl(ctx, (int)E, M, n, ss, data, sigma2, psf, G, epochs_per_group, out);
+  if (background) {
+    // the single-workgroup update per star (the one-star fit's own form at these sizes); larger stamps are fitted one by one
+    if (!lc_joint_groups_background_supported(n, ss))
+      LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_joint_create_groups_background: stamp sizes with a single-workgroup update only (n = 16, 24, 32 at ss = 2, n = 16 at ss = 1)");
+  }
+  return joint_create_impl(ctx, (int)E, M, n, ss, data, sigma2, psf, G, epochs_per_group, out, background);
 }
 static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const float *data, const float *sigma2,
-                             const float *psf, int G, const int32_t *epochs_per_group, lc_joint **out) {
+                             const float *psf, int G, const int32_t *epochs_per_group, lc_joint **out, bool background) {
   if (!ctx || !out || !data || !sigma2 || !psf || E <= 0 || M < 0) {
     if (ctx) ctx->err = "lc_joint_create: invalid argument";
     return LC_ERR_INVALID;
   }
-  // grouped objects run the point-source-only kernel and nothing else: no spectra, no background work space
-  const bool lean = G > 0;
+  // grouped objects run the point-source-only kernel and nothing else: no spectra, no background work space (except the
+  // per-star background form, which has them all: bgG stars' worth of the per-star blocks)
+  const bool lean = G > 0 && !background;
+  const int bgG = background ? G : 1;
   if (M > kMaxSources) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "at most 8 point sources");
   const JointVariant *v = find_jv(n, ss, E, ctx->n_cu);
   if (!v) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "no joint-fit kernel instantiated for this stamp size");
@@ -1269,8 +1314,9 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
     return rc;             \
   }
   const int GM = std::max(G, 1) * M;
-  const int sizes[LC_P_COUNT] = {E * M, GM, GM, E, E, E, (int)NN, E};
+  const int sizes[LC_P_COUNT] = {E * M, GM, GM, E, E, E, (int)NN * bgG, E};
   j->G = G;
+  j->bg = background;
   for (int k = 0; k < LC_P_COUNT; ++k) {
     j->psize[k] = sizes[k];
     TRY(dmalloc(j, &j->par[k], sizes[k]));
@@ -1295,19 +1341,19 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
   TRY(dmalloc(j, &j->fisher, E * M));
   j->shared_count = (int)NN + 4 * M + 2;
   TRY(dmalloc(j, &j->shared, j->shared_count));
-  TRY(dmalloc(j, &j->W, lean ? 1 : (size_t)(j->J + 1) * NN));
+  TRY(dmalloc(j, &j->W, lean ? 1 : (size_t)bgG * (j->J + 1) * NN));
   TRY(dmalloc(j, &j->norms, j->J + 1));
-  TRY(dmalloc(j, &j->qscr, lean ? 1 : (size_t)(j->J + 1) * NN));
+  TRY(dmalloc(j, &j->qscr, lean ? 1 : (size_t)bgG * (j->J + 1) * NN));
   TRY(dmalloc(j, &j->out_loss, 4));
-  TRY(dmalloc(j, &j->greg, NN));
-  TRY(dmalloc(j, &j->regs, 4 + 3 * kMaxSources + 4));
-  const bool cluster_ok = v->ek_cluster && !lean && E <= ctx->n_cu / 2;  // (at least two workgroups per epoch, all resident)
+  TRY(dmalloc(j, &j->greg, (size_t)bgG * NN));
+  TRY(dmalloc(j, &j->regs, (size_t)bgG * kRegsStride));
+  const bool cluster_ok = v->ek_cluster && G == 0 && E <= ctx->n_cu / 2;  // (at least two workgroups per epoch, all resident)
   if ((v->gspec || cluster_ok) && !lean) TRY(dmalloc(j, &j->spec, (size_t)E * N * ((KH + 15) / 16 * 16)));  // rows padded to 128-byte lines (JointCfg::KS)
   if ((v->gspec || cluster_ok) && !lean) TRY(dmalloc(j, &j->part, (size_t)E * kMaxParts * (4 + 3 * kMaxSources)));
   if (cluster_ok) TRY(dmalloc(j, &j->cl_ctr, (size_t)(E + 1) * kClStride));
   if (!lean) TRY(dmalloc(j, &j->chain_flags, kChainBlocks + 32));
   if (v->gspec && !lean) TRY(dmalloc(j, &j->tshift, (size_t)E * 2));
-  if (lean) {
+  if (G > 0) {
     std::vector<int> grp(E);
     j->gstart.assign(G + 1, 0);
     for (int g = 0; g < G; ++g) {
@@ -1316,8 +1362,14 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
     }
     TRY(dmalloc(j, &j->group_dev, E));
     TRY(h2d(j, j->group_dev, grp.data(), grp.size() * sizeof(int)));
-    TRY(dmalloc(j, &j->views_dev, G));
-    TRY(dmalloc(j, &j->shared_g, (size_t)G * (4 * M + 2)));
+    TRY(dmalloc(j, &j->views_dev, (size_t)G * (background ? 3 : 1)));
+    TRY(dmalloc(j, &j->shared_g, (size_t)G * ((background ? NN : 0) + 4 * M + 2)));
+    if (background) {
+      TRY(dmalloc(j, &j->gstart_dev, G + 1));
+      TRY(h2d(j, j->gstart_dev, j->gstart.data(), j->gstart.size() * sizeof(int)));
+      LC_HIP(ctx, hipFuncSetAttribute((const void *)v->ek_grp, hipFuncAttributeMaxDynamicSharedMemorySize, v->e_lds));
+      LC_HIP(ctx, hipFuncSetAttribute((const void *)v->uk_grp, hipFuncAttributeMaxDynamicSharedMemorySize, v->u_lds));
+    }
     TRY(dmalloc(j, &j->a_ref_g, (size_t)G * kMaxSources));
     TRY(dmalloc(j, &j->out_loss_g, G));
   }
@@ -1481,7 +1533,7 @@ int lc_joint_set_param(lc_joint *j, int which, const float *values, int count) {
         break;
       }
   }
-  if (j->G > 0 && which == LC_P_H && j->h_nonzero) {
+  if (j->G > 0 && !j->bg && which == LC_P_H && j->h_nonzero) {
     j->h_nonzero = false;  // (nothing was stored)
     LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry has no background: h must stay zero");
   }
@@ -1535,7 +1587,7 @@ int lc_joint_set_free(lc_joint *j, const int32_t *free_mask) {
   if (!j || !free_mask) return LC_ERR_INVALID;
   LC_ENTER(j->ctx);
   if (free_mask[LC_P_ALPHA]) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "alpha is never optimised (roi_modelling.py:221-222)");
-  if (j->G > 0 && free_mask[LC_P_H]) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry has no background grid");
+  if (j->G > 0 && !j->bg && free_mask[LC_P_H]) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry has no background grid");
   for (int k = 0; k < LC_P_COUNT; ++k) j->free_mask[k] = free_mask[k] ? 1 : 0;
   lc_joint_param_history_end(j);  // (its row layout follows the free blocks)
   // a new optimisation starts: reset the moments and the iteration counter
@@ -1549,8 +1601,10 @@ int lc_joint_set_free(lc_joint *j, const int32_t *free_mask) {
 int lc_joint_set_loss(lc_joint *j, const lc_joint_loss_cfg *cfg, const float *W) {
   if (!j || !cfg) return LC_ERR_INVALID;
   LC_ENTER(j->ctx);
-  if (j->G > 0 && (cfg->lam_pts_source != 0.f || cfg->n_prior > 0 || W))
+  if (j->G > 0 && !j->bg && (cfg->lam_pts_source != 0.f || cfg->n_prior > 0 || W))
     LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry: no point-source starlet term, prior or weight cube");
+  if (j->bg && (cfg->lam_pts_source != 0.f || cfg->n_prior > 0))
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry with backgrounds: no point-source starlet term or prior");
   j->cfg = *cfg;
   j->n_prior = 0;
   if (cfg->n_prior > 0) {
@@ -1568,7 +1622,13 @@ int lc_joint_set_loss(lc_joint *j, const lc_joint_loss_cfg *cfg, const float *W)
     j->n_prior = j->M;
   }
   j->cfg.prior_cx_mean = j->cfg.prior_cx_sigma = j->cfg.prior_cy_mean = j->cfg.prior_cy_sigma = nullptr;
-  if (W) {
+  if (W && j->bg) {  // [G][J][N][N] -> the per-star blocks of (J + 1) N^2
+    const size_t blk = (size_t)j->J * j->N * j->N, stride = (size_t)(j->J + 1) * j->N * j->N;
+    LC_HIP(j->ctx, hipMemcpy2DAsync(j->W, stride * sizeof(float), W, blk * sizeof(float), blk * sizeof(float), j->G,
+                                    hipMemcpyHostToDevice, j->ctx->stream));
+    LC_HIP(j->ctx, hipStreamSynchronize(j->ctx->stream));
+    j->have_W = true;
+  } else if (W) {
     int rc = h2d(j, j->W, W, (size_t)j->J * j->N * j->N * sizeof(float));
     if (rc) return rc;
     j->have_W = true;
@@ -1579,10 +1639,82 @@ int lc_joint_set_loss(lc_joint *j, const lc_joint_loss_cfg *cfg, const float *W)
 }
 
 namespace {
+int ensure_group_hist(lc_joint *j, int needed);
+// Batched star photometry with backgrounds: the three sets of per-star views (lc_joint::bg) - [0, G) the fused reduction +
+// update of the device loop, [G, 2G) the regulariser launch in front of it, [2G, 3G) the final-loss launch (iteration
+// t_final) and the reductions over each star's epochs - each field what launch_update / launch_reduce hand a one-star fit of
+// that star in the same role
+int upload_bg_views(lc_joint *j, const lc_adabelief_cfg *cfg, int t_final) {
+  const int G = j->G, M = j->M;
+  const size_t NN = (size_t)j->N * j->N, WS = (size_t)(j->J + 1) * NN, SG = NN + 4 * M + 2;
+  const bool rh = reg_h_on(j);
+  std::vector<JointUpdArgs> views(3 * (size_t)G);
+  for (int g = 0; g < G; ++g) {
+    JointUpdArgs B;
+    std::memset(&B, 0, sizeof(B));
+    const int e0 = j->gstart[g];
+    B.E = j->gstart[g + 1] - e0;
+    B.M = M;
+    B.ss = j->ss;
+    const size_t off[LC_P_COUNT] = {(size_t)e0 * M, (size_t)g * M, (size_t)g * M, (size_t)e0, (size_t)e0, (size_t)e0, g * NN, (size_t)e0};
+    for (int k = 0; k < LC_P_COUNT; ++k) {
+      B.free_mask[k] = j->free_mask[k];
+      B.par[k] = j->par[k] + off[k];
+      B.pm[k] = j->pm[k] + off[k];
+      B.ps[k] = j->ps[k] + off[k];
+    }
+    B.h = B.par[LC_P_H];
+    B.mh = B.pm[LC_P_H];
+    B.sh = B.ps[LC_P_H];
+    B.greg = j->greg + g * NN;
+    B.regs = j->regs + (size_t)g * kRegsStride;
+    B.shared = B.shared_w = j->shared_g + g * SG;
+    B.a_ref = j->a_ref_g + (size_t)g * kMaxSources;
+    B.W = j->have_W ? j->W + g * WS : nullptr;
+    B.norms = j->norms;
+    B.qscr = j->qscr + g * WS;
+    B.g_a = j->g_a + (size_t)e0 * M;
+    B.g_cx_e = j->g_cx_e + (size_t)e0 * M;
+    B.g_cy_e = j->g_cy_e + (size_t)e0 * M;
+    B.g_dx = j->g_dx + e0;
+    B.g_dy = j->g_dy + e0;
+    B.g_mean = j->g_mean + e0;
+    B.chi2_e = j->chi2_e + e0;
+    B.hist = j->ghist + (size_t)g * j->ghist_cap;
+    B.out_loss = j->out_loss_g + g;
+    B.lam_sc = rh ? j->cfg.lam_scales : 0.f;
+    B.lam_hf = rh ? j->cfg.lam_hf : 0.f;
+    B.lam_pos = rh ? j->cfg.lam_positivity : 0.f;
+    B.lam_pos_ps = j->cfg.lam_positivity_ps;
+    B.lam_fu = j->cfg.lam_flux_uniformity;
+    if (cfg) B.ab = *cfg; else lc_adabelief_defaults(&B.ab);
+    JointUpdArgs &U = views[g], &R = views[G + g], &F = views[2 * G + g];
+    U = R = F = B;
+    U.mode = 1;
+    U.reg_mode = 2;
+    R.mode = 0;
+    R.reg_mode = 1;
+    F.mode = 0;
+    F.reg_mode = 0;
+    F.t = t_final;
+    if (!cfg) lc_adabelief_defaults(&F.ab);
+    adabelief_schedule(F.ab, t_final, F.lr, F.bc1, F.bc2);
+  }
+  return h2d(j, j->views_dev, views.data(), views.size() * sizeof(JointUpdArgs));
+}
+// sums over each star's own epochs of HG (and of the per-epoch scalars) into the stars' reduced blocks (views [2G, 3G))
+int launch_reduce_groups(lc_joint *j, int need_h, hipStream_t q) {
+  const int NN = j->N * j->N;
+  hipLaunchKernelGGL(joint_reduce_groups_kernel, dim3(NN / kRedPix + 1, j->G), dim3(kRedThreads), 0, q, j->views_dev + 2 * j->G, NN,
+                     need_h, j->HG, j->gstart_dev);
+  LC_HIP(j->ctx, hipGetLastError());
+  return LC_OK;
+}
 int propagate_noise_device(lc_joint *j) {
   const int N = j->N, ss = j->ss, E = j->E, J = j->J, c = (N - 1) / 2, shift = ss * (j->n / 2) - c;
   const size_t NN = (size_t)N * N, ENN = (size_t)E * NN;
   int rc;
+  if (j->bg && ((rc = ensure_group_hist(j, j->iters_done + 2)) || (rc = upload_bg_views(j, nullptr, j->iters_done)))) return rc;
   if (!j->nz_a) {
     if ((rc = dmalloc(j, &j->nz_a, ENN)) || (rc = dmalloc(j, &j->nz_b, ENN)) || (rc = dmalloc(j, &j->nz_c, ENN)) ||
         (rc = dmalloc(j, &j->nz_up, ENN)) || (rc = dmalloc(j, &j->nz_scene, ENN)) ||
@@ -1603,9 +1735,16 @@ int propagate_noise_device(lc_joint *j) {
     LC_HIP(j->ctx, hipGetLastError());
     if ((rc = launch_aux(j, 4, j->nz_scene, nullptr, j->St_alt, nullptr))) return rc;       // spectra of kappa^2
     if ((rc = launch_aux(j, 3, j->nz_up, j->St_alt, nullptr, j->HG))) return rc;            // up0(w_e) (*) kappa_e^2
-    if ((rc = launch_reduce(j, 1))) return rc;                                              // sum over the epochs
-    hipLaunchKernelGGL(nz_sqrt_kernel, dim3((unsigned)((NN + kNzThreads - 1) / kNzThreads)), block, 0, q, (int)NN, j->shared,
-                       j->W + (size_t)s * NN);
+    if (j->bg) {   // (batched stars: the sum over each star's epochs, its own levels)
+      if ((rc = launch_reduce_groups(j, 1, q))) return rc;
+      for (int g = 0; g < j->G; ++g)
+        hipLaunchKernelGGL(nz_sqrt_kernel, dim3((unsigned)((NN + kNzThreads - 1) / kNzThreads)), block, 0, q, (int)NN,
+                           j->shared_g + g * (NN + 4 * j->M + 2), j->W + ((size_t)g * (J + 1) + s) * NN);
+    } else {
+      if ((rc = launch_reduce(j, 1))) return rc;                                              // sum over the epochs
+      hipLaunchKernelGGL(nz_sqrt_kernel, dim3((unsigned)((NN + kNzThreads - 1) / kNzThreads)), block, 0, q, (int)NN, j->shared,
+                         j->W + (size_t)s * NN);
+    }
     LC_HIP(j->ctx, hipGetLastError());
     std::swap(cur, nxt);
   }
@@ -1616,14 +1755,14 @@ int propagate_noise_device(lc_joint *j) {
 int lc_joint_propagate_noise(lc_joint *j, float *W_out) {
   if (!j) return LC_ERR_INVALID;
   LC_ENTER(j->ctx);
-  if (j->G > 0) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_propagate_noise: not available on a batched star-photometry object");
+  if (j->G > 0 && !j->bg) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_propagate_noise: not available on a batched star-photometry object");
   const int N = j->N, n = j->n, ss = j->ss, E = j->E, c = (N - 1) / 2;
   const size_t NN = (size_t)N * N, nn = (size_t)n * n;
-  if (!std::getenv("LCMI_NOISE_HOST")) {
+  if (!std::getenv("LCMI_NOISE_HOST") || j->bg) {
     int rc = propagate_noise_device(j);
     if (rc) return rc;
     j->have_W = true;
-    if (W_out && (rc = d2h(j, W_out, j->W, (size_t)(j->J + 1) * NN * sizeof(float)))) return rc;
+    if (W_out && (rc = d2h(j, W_out, j->W, (size_t)(j->bg ? j->G : 1) * (j->J + 1) * NN * sizeof(float)))) return rc;
     return LC_OK;
   }
   // host path (double-precision FFT convolutions, threaded), kept as an independent cross-check: LCMI_NOISE_HOST=1
@@ -2013,15 +2152,16 @@ int lc_joint_deconvolved(lc_joint *j, int epoch, float *scene, float *background
   LC_ENTER(j->ctx);
   const size_t NN = (size_t)j->N * j->N;
   // (a batched star-photometry object: `epoch` counts over the epochs of all stars; the positions are those of its star)
-  size_t coff = 0;
+  size_t coff = 0, hoff = 0;
   if (j->G > 0) {
     int g = 0;
     while (g + 1 < j->G && epoch >= j->gstart[g + 1]) ++g;
     coff = (size_t)g * j->M;
+    if (j->bg) hoff = (size_t)g * NN;   // (and the background grid of its star)
   }
   hipLaunchKernelGGL(joint_scene_kernel, dim3(64), dim3(256), 0, j->ctx->stream, j->N, j->ss, j->M, epoch, j->par[LC_P_A],
                      j->par[LC_P_CX] + coff, j->par[LC_P_CY] + coff, j->par[LC_P_DX], j->par[LC_P_DY], j->par[LC_P_ALPHA],
-                     j->par[LC_P_H], j->scene2, j->scene2 + NN);
+                     j->par[LC_P_H] + hoff, j->scene2, j->scene2 + NN);
   LC_HIP(j->ctx, hipGetLastError());
   int rc;
   if (scene && (rc = d2h(j, scene, j->scene2, NN * sizeof(float)))) return rc;
@@ -2185,9 +2325,31 @@ int group_update(lc_joint *j, int mode, int t, const lc_adabelief_cfg *cfg, int 
   LC_HIP(j->ctx, hipGetLastError());
   return LC_OK;
 }
+// Per-star backgrounds (lc_joint::bg): the regulariser of the stars [g0, g1) in front of their epoch launch (what the one-star
+// loop runs on its second stream, here in stream order), and the fused reduction + update behind it
+int part_reg(lc_joint *j, int g0, int g1, hipStream_t q) {
+  if (!j->bg) return LC_OK;
+  hipLaunchKernelGGL(j->v->uk_grp, dim3(g1 - g0), dim3(j->v->u_thr), j->v->u_lds, q, j->views_dev + j->G + g0);
+  LC_HIP(j->ctx, hipGetLastError());
+  return LC_OK;
+}
+int part_update(lc_joint *j, int t, const lc_adabelief_cfg *cfg, int g0, int g1, hipStream_t q) {
+  if (!j->bg) return group_update(j, 1, t, cfg, g0, g1, q);
+  lc_adabelief_cfg ab;
+  if (cfg) ab = *cfg; else lc_adabelief_defaults(&ab);
+  float lr, bc1, bc2;
+  adabelief_schedule(ab, t, lr, bc1, bc2);
+  hipLaunchKernelGGL(joint_reduce_update_groups_kernel, dim3(j->N * j->N / kRedPix + 2, g1 - g0), dim3(kRedThreads), 0, q,
+                     j->views_dev + g0, j->N, j->HG, j->gstart_dev + g0, 1, t, lr, bc1, bc2);
+  LC_HIP(j->ctx, hipGetLastError());
+  return LC_OK;
+}
 int run_adabelief_groups(lc_joint *j, int n_iter, const lc_adabelief_cfg *cfg) {
+  // (per-star backgrounds: the one-star loop's form with the regulariser on - h free, starlet or positivity weight set)
+  if (j->bg && !(j->free_mask[LC_P_H] && reg_h_on(j)))
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "batched star photometry with backgrounds: h must be free and regularised (otherwise use lc_joint_create_groups)");
   int rc = ensure_group_hist(j, j->iters_done + n_iter + 2);
-  if (rc || (rc = upload_group_views(j, cfg))) return rc;
+  if (rc || (rc = (j->bg ? upload_bg_views(j, cfg, j->iters_done) : upload_group_views(j, cfg)))) return rc;
   // The stars are independent fits, and the update of a batch is a launch of two short blocks per star (a chain of memory
   // round trips, ~15 us with the machine idle around it).  The batch therefore runs as K parts on K streams, each part its
   // own sequence of kernel pairs, the first launches staggered: while one part steps, the point-source kernels of the
@@ -2200,9 +2362,10 @@ int run_adabelief_groups(lc_joint *j, int n_iter, const lc_adabelief_cfg *cfg) {
   K = std::max(1, std::min(std::min(K, j->G), 8));
   if (K == 1) {
     for (int it = 0; it < n_iter; ++it) {
+      if ((rc = part_reg(j, 0, j->G, j->ctx->stream))) return rc;
       int need = launch_epochs(j, 0, 0, false, nullptr);
       if (need < 0) return need;
-      if ((rc = group_update(j, 1, j->iters_done, cfg))) return rc;
+      if ((rc = part_update(j, j->iters_done, cfg, 0, j->G, j->ctx->stream))) return rc;
       j->iters_done += 1;
     }
     return LC_OK;
@@ -2235,10 +2398,11 @@ int run_adabelief_groups(lc_joint *j, int n_iter, const lc_adabelief_cfg *cfg) {
     for (int k = 0; k < K && !rc; ++k) {
       hipStream_t q = stream_of(k);
       if (it == 0 && k > 0) rc = (hipStreamWaitEvent(q, j->gevents[k - 1], 0) == hipSuccess) ? LC_OK : LC_ERR_DEVICE;
+      if (!rc) rc = part_reg(j, gb[k], gb[k + 1], q);
       int need = rc ? -1 : launch_epochs(j, 0, 0, false, nullptr, j->gstart[gb[k]], j->gstart[gb[k + 1]], q);
       if (!rc && need < 0) rc = need;
       if (!rc && it == 0 && k < K - 1) rc = (hipEventRecord(j->gevents[k], q) == hipSuccess) ? LC_OK : LC_ERR_DEVICE;
-      if (!rc) rc = group_update(j, 1, j->iters_done, cfg, gb[k], gb[k + 1], q);
+      if (!rc) rc = part_update(j, j->iters_done, cfg, gb[k], gb[k + 1], q);
     }
     if (!rc) j->iters_done += 1;
   }
@@ -2255,10 +2419,14 @@ int lc_joint_get_group_loss_history(lc_joint *j, float *history, int count_per_g
   if (!j || !history || j->G <= 0 || count_per_group < j->iters_done + 1) return LC_ERR_INVALID;
   LC_ENTER(j->ctx);
   int rc = ensure_group_hist(j, j->iters_done + 2);
-  if (rc || (rc = upload_group_views(j, nullptr))) return rc;
+  if (rc || (rc = (j->bg ? upload_bg_views(j, nullptr, j->iters_done) : upload_group_views(j, nullptr)))) return rc;
   int need = launch_epochs(j, 0, 0, false, nullptr);  // loss of the final parameters -> hist[g][T]
   if (need < 0) return need;
-  if ((rc = group_update(j, 0, j->iters_done, nullptr))) return rc;
+  if (j->bg) {   // (the one-star fit's final-loss evaluation: reduction, then the single-workgroup kernel with the regulariser inline)
+    if ((rc = launch_reduce_groups(j, need, j->ctx->stream))) return rc;
+    hipLaunchKernelGGL(j->v->uk_grp, dim3(j->G), dim3(j->v->u_thr), j->v->u_lds, j->ctx->stream, j->views_dev + 2 * j->G);
+    LC_HIP(j->ctx, hipGetLastError());
+  } else if ((rc = group_update(j, 0, j->iters_done, nullptr))) return rc;
   LC_HIP(j->ctx, hipMemcpy2DAsync(history, (size_t)count_per_group * sizeof(float), j->ghist, (size_t)j->ghist_cap * sizeof(float),
                                   (size_t)(j->iters_done + 1) * sizeof(float), j->G, hipMemcpyDeviceToHost, j->ctx->stream));
   LC_HIP(j->ctx, hipStreamSynchronize(j->ctx->stream));

@@ -731,18 +731,19 @@ __global__ __launch_bounds__(kGmThreads) void joint_update_groups_kernel(const J
 // resident blocks per CU leave 112 of the 512 registers per lane and SIMD, which is what a wave of every kernel of the
 // regulariser chain must fit in (joint_reg_fused.h) - a late chain must be schedulable while this kernel waits for it.
 constexpr int kUpdMaxTiles = 4;  // tiles per block the kernel below holds side by side (the host never asks for more)
-__global__ __launch_bounds__(kRedThreads) void joint_reduce_update_kernel(JointUpdArgs A, int N, const float *HG, int tiles) {
+// (block bx of the launch; lr, bc1, bc2, mode_ov, t_ov: joint_update_groups_kernel's arguments - the one-fit kernel passes its own)
+__device__ __forceinline__ void joint_reduce_update_block(const JointUpdArgs &A, int bx, int N, const float *HG, int tiles, float lr,
+                                                          float bc1, float bc2, int mode_ov, int t_ov) {
   static_assert(kRedThreads == kGmThreads, "one block size");
   __shared__ float4 part[kRedParts][kRedPix / 4];
   __shared__ double lanes[kRedThreads];
   const int E = A.E, M = A.M, NN = N * N;
   const int nimg = NN / kRedPix / tiles;  // image blocks
   const int tid = threadIdx.x;
-  const float lr = A.lr, bc1 = A.bc1, bc2 = A.bc2;
   // The two single blocks come FIRST in the grid: the scalar block is the longest chain of the launch (tools/update_stamps.py)
   // and, dispatched behind the image blocks, it waited for one of them to leave a CU before it even started (4.5 us into the
   // launch at 512 image blocks, 10.9 us at the 1024 of a 256 x 256 grid).  bid: block among the image blocks, then the two.
-  const int bid = ((int)blockIdx.x >= 2) ? (int)blockIdx.x - 2 : nimg + (int)blockIdx.x;
+  const int bid = (bx >= 2) ? bx - 2 : nimg + bx;
   if (bid < nimg) {
     // The tiles of a block side by side: state and slab loads of every tile requested first (one memory round trip for the
     // block instead of one per tile), the tiles combined one after the other through the LDS buffer, the regulariser's flag,
@@ -797,7 +798,7 @@ __global__ __launch_bounds__(kRedThreads) void joint_reduce_update_kernel(JointU
     return;
   }
   if (bid == nimg + 1) {  // shifts and sky levels: nothing to wait for
-    gm_small_blocks(A, N, lr, bc1, bc2, nullptr, 2);
+    gm_small_blocks(A, N, lr, bc1, bc2, nullptr, 2, nullptr, nullptr, mode_ov, t_ov);
     return;
   }
   __shared__ float scl[4 * kMaxSources + 2];
@@ -823,8 +824,29 @@ __global__ __launch_bounds__(kRedThreads) void joint_reduce_update_kernel(JointU
     __syncthreads();
   }
   LC_USTAMP(4);
-  gm_small_blocks(A, N, lr, bc1, bc2, scl, 1, &pre, have_regs ? regl : nullptr);
+  gm_small_blocks(A, N, lr, bc1, bc2, scl, 1, &pre, have_regs ? regl : nullptr, mode_ov, t_ov);
   LC_USTAMP(8);
+}
+__global__ __launch_bounds__(kRedThreads) void joint_reduce_update_kernel(JointUpdArgs A, int N, const float *HG, int tiles) {
+  joint_reduce_update_block(A, (int)blockIdx.x, N, HG, tiles, A.lr, A.bc1, A.bc2, -1, -1);
+}
+
+// Batched star photometry with a background grid per star (lc_joint_create_groups_background).  Grid (NN / kRedPix + 2, G):
+// row g is, for star g - its epochs [gstart[g], gstart[g + 1]), its view - exactly the launch above for a fit of that star
+// alone (one tile per block, regulariser in greg / regs of the view, nothing to wait for: stream order).
+__global__ __launch_bounds__(kRedThreads) void joint_reduce_update_groups_kernel(const JointUpdArgs *__restrict__ views, int N,
+                                                                                 const float *HG, const int *gstart, int mode,
+                                                                                 int t, float lr, float bc1, float bc2) {
+  const JointUpdArgs &A = views[blockIdx.y];
+  joint_reduce_update_block(A, (int)blockIdx.x, N, HG + (size_t)gstart[blockIdx.y] * N * N, 1, lr, bc1, bc2, mode, t);
+}
+// ... and the reduction over each star's epochs alone (joint_reduce_kernel per star: final loss, noise propagation); grid
+// (NN / kRedPix + 1, G), the sums go to the star's reduced block (view.shared_w)
+__global__ __launch_bounds__(kRedThreads) void joint_reduce_groups_kernel(const JointUpdArgs *__restrict__ views, int NN, int need_h,
+                                                                          const float *HG, const int *gstart) {
+  const JointUpdArgs &A = views[blockIdx.y];
+  joint_reduce_block((int)blockIdx.x, A.E, A.M, NN, need_h, HG + (size_t)gstart[blockIdx.y] * NN, A.g_cx_e, A.g_cy_e, A.chi2_e,
+                     A.par[LC_P_A], A.a_ref, A.shared_w);
 }
 
 // The same launch with the T_e^T step folded into the reduction (global-spectrum kernels, every epoch a pure translation):

@@ -52,6 +52,7 @@ struct JointArgs {
   float2 *St_out;             // [E][L/2+1][L]
   float *conv_out;            // [E][N][N]
   // batched star photometry (point-source-only kernel): epoch -> star; the shared positions are cx[group[e] * M + i]
+  // (GRP build of the epoch kernel, per-star background: also h + group[e] * N * N, and block b serves epoch e_off + b)
   const int *group;           // [E] or null
   // the T_e^T step is applied by the reduction itself (joint_stencil_update_kernel): phase D leaves the scene-gradient rows
   // in the spectrum scratch and writes no slab
@@ -81,6 +82,7 @@ struct JointArgs {
   unsigned int chain_seq;
   unsigned int *chain_err;
   int wait_block;
+  int e_off;                  // GRP build: the first epoch of this launch (see `group`)
 };
 constexpr int kClStride = 32;    // flag words per epoch (one 128-byte line; kMaxParts <= 16 of them in use)
 constexpr int kClBarriers = 6;   // start | A | B | C | B' | C' | D: every cluster launch passes exactly six syncs
@@ -307,11 +309,12 @@ __device__ __forceinline__ void joint_epoch_totals(const JointArgs &A, int e, in
 // spectrum travels between the launches through global memory, and the launch boundaries are the synchronisation (no
 // waiting inside a kernel).  An epoch that would occupy one CU out of two then uses the whole machine, and every launch
 // holds the registers of one phase only.  The reductions of the epoch are finished by joint_epoch_finish_kernel.
-template <class C, bool AUX = false, int PHASE = 0>
+template <class C, bool AUX = false, int PHASE = 0, bool GRP = false>
 // (Column phases built for two workgroups per CU - 128 registers, 31 to 74 of them spilled - measured slower than one at every
 //  split of the C5 shard: 367 - 405 us per iteration against 338.)
 __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
   static_assert(PHASE == 0 || (C::GSPEC && !AUX), "one phase per launch: spectrum in global memory");
+  static_assert(!GRP || (PHASE == 0 && !AUX), "per-star background: the one-workgroup kernel");
   if (A.upd_signal && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)   // (JointArgs: the update before this launch is complete)
     __hip_atomic_store(A.upd_signal, A.upd_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (A.chain_flag && (int)blockIdx.x == A.wait_block) {   // (JointArgs: the extra block that waits for the regulariser chain)
@@ -344,7 +347,7 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
   constexpr bool ONE = (PHASE == 0) && !C::GSPEC;
   const int part = CL ? (int)((blockIdx.x >> 3) % (unsigned)A.cl_parts) : (ONE ? 0 : (int)blockIdx.y);
   const int nparts = CL ? A.cl_parts : (ONE ? 1 : (int)gridDim.y);
-  const int e = CL ? (int)(8 * ((blockIdx.x >> 3) / (unsigned)A.cl_parts) + (blockIdx.x & 7)) : (int)blockIdx.x;
+  const int e = CL ? (int)(8 * ((blockIdx.x >> 3) / (unsigned)A.cl_parts) + (blockIdx.x & 7)) : (int)blockIdx.x + (GRP ? A.e_off : 0);
   if constexpr (CL) {
     if (e >= A.E) return;  // (the grid is rounded up to whole groups of eight epochs: no such block takes part in anything)
   }
@@ -381,6 +384,20 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
   };
   const int pw = part * C::NW + wid, PWS = nparts * C::NW;  // this wave among the epoch's waves, their number
   const int M = A.M;
+  // this epoch's background grid and point-source positions (GRP: those of the epoch's star in a batch; otherwise the
+  // arguments themselves, read where they are used - the one-star build compiles as it did without the batched form)
+  // (GRP: A.group[e] is read at every use - a workgroup-uniform word, a scalar load from the scalar cache.  Looked up once
+  //  into pointers held across the kernel, the GRP build contracted its multiply-adds differently from the one-star build
+  //  (two packed FMAs fewer at N = 32) and the stars of a batch no longer ended bit for bit where their own fits end.)
+  auto hb = [&]() -> const float * {
+    if constexpr (GRP) return A.h + (size_t)A.group[e] * (N * N); else return A.h;
+  };
+  auto cxb = [&]() -> const float * {
+    if constexpr (GRP) return A.cx + A.group[e] * M; else return A.cx;
+  };
+  auto cyb = [&]() -> const float * {
+    if constexpr (GRP) return A.cy + A.group[e] * M; else return A.cy;
+  };
   const float c0 = (N - 1) * 0.5f;
   const float al = A.alpha[e] * 0.017453292519943295f;
   const float ca = cosf(al), sa = sinf(al);
@@ -415,8 +432,8 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
     const float nrm = 0.3989422804014327f / kSigmaG;
     for (int idx = tid; idx < M * N; idx += C::NTHR) {
       const int i = idx / N, p = idx % N;
-      const float X = c0 + SS * (ca * A.cx[i] - sa * A.cy[i] + dxe);
-      const float Y = c0 + SS * (sa * A.cx[i] + ca * A.cy[i] + dye);
+      const float X = c0 + SS * (ca * cxb()[i] - sa * cyb()[i] + dxe);
+      const float Y = c0 + SS * (sa * cxb()[i] + ca * cyb()[i] + dye);
       const float tx = (float)p - X, ty = (float)p - Y;
       GX[i * N + p] = nrm * expf(-0.5f * tx * tx * inv_s2);
       GY[i * N + p] = nrm * expf(-0.5f * ty * ty * inv_s2);
@@ -488,7 +505,7 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
     if constexpr (HPIPE) {  // (the row index is clamped: an idle group loads valid rows it never uses)
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const float *src = A.h + (size_t)min(max(u0 + iyc + r, 0), N - 1) * N;
+        const float *src = hb() + (size_t)min(max(u0 + iyc + r, 0), N - 1) * N;
 #pragma unroll
         for (int t = 0; t < N / (4 * LPF); ++t) pre[r * (N / (4 * LPF)) + t] = *(const float4 *)&src[4 * (l16 + LPF * t)];
       }
@@ -505,7 +522,7 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
             *(float4 *)&hrow[r * N + ((x + hskew) & HMASK)] = pre[r * (N / (4 * LPF)) + t];
           }
         } else {
-          const float *src = A.h + (size_t)min(max(u0 + iyc + r, 0), N - 1) * N;
+          const float *src = hb() + (size_t)min(max(u0 + iyc + r, 0), N - 1) * N;
 #pragma unroll
           for (int t = 0; t < N / LPF; ++t) {
             const int x = l16 + LPF * t;
@@ -519,7 +536,7 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
     if (active) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const float *src = A.h + (size_t)min(max(u0 + iyc + r, 0), N - 1) * N;
+        const float *src = hb() + (size_t)min(max(u0 + iyc + r, 0), N - 1) * N;
         if constexpr (HPIPE) {
 #pragma unroll
           for (int t = 0; t < N / (4 * LPF); ++t) {
@@ -913,9 +930,9 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
         if (use_h) {
           float Xs, Ys, t0, t1;
           sample_coords(u0, v, c0, ca, sa, sdx, sdy, Xs, Ys);
-          s0 += bilinear_h<N>(A.h, Xs, Ys, t0, t1);
+          s0 += bilinear_h<N>(hb(), Xs, Ys, t0, t1);
           sample_coords(u0 + 1, v, c0, ca, sa, sdx, sdy, Xs, Ys);
-          s1 += bilinear_h<N>(A.h, Xs, Ys, t0, t1);
+          s1 += bilinear_h<N>(hb(), Xs, Ys, t0, t1);
         }
         z = make_float2(s0, s1);
       }
@@ -1384,11 +1401,11 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
         } else if (use_h) {
           float Xs, Ys, hx, hy;
           sample_coords(u0, v, c0, ca, sa, sdx, sdy, Xs, Ys);
-          bilinear_h<N>(A.h, Xs, Ys, hx, hy);
+          bilinear_h<N>(hb(), Xs, Ys, hx, hy);
           acc_dx = fmaf(g.x, SS * (sa * hy - ca * hx), acc_dx);
           acc_dy = fmaf(g.x, -SS * (sa * hx + ca * hy), acc_dy);
           sample_coords(u0 + 1, v, c0, ca, sa, sdx, sdy, Xs, Ys);
-          bilinear_h<N>(A.h, Xs, Ys, hx, hy);
+          bilinear_h<N>(hb(), Xs, Ys, hx, hy);
           acc_dx = fmaf(g.y, SS * (sa * hy - ca * hx), acc_dx);
           acc_dy = fmaf(g.y, -SS * (sa * hx + ca * hy), acc_dy);
         }
@@ -1715,21 +1732,27 @@ __device__ __forceinline__ void reduce_scalars(int E, int M, int NN, const float
     if (scl) scl[4 * M + 1] = (float)E;
   }
 }
-__global__ __launch_bounds__(kRedThreads) void joint_reduce_kernel(int E, int M, int NN, int need_h, const float *HG,
-                                                                    const float *g_cx_e, const float *g_cy_e,
-                                                                    const float *chi2_e, const float *a,
-                                                                    const float *a_ref, float *shared) {
+// (block bx of the launch; also the per-star form joint_reduce_groups_kernel)
+__device__ __forceinline__ void joint_reduce_block(int bx, int E, int M, int NN, int need_h, const float *HG, const float *g_cx_e,
+                                                   const float *g_cy_e, const float *chi2_e, const float *a, const float *a_ref,
+                                                   float *shared) {
   __shared__ float4 part[kRedParts][kRedPix / 4];
   const int nimg = NN / kRedPix;
   const int tid = threadIdx.x;
-  if ((int)blockIdx.x < nimg) {
-    const int px0 = blockIdx.x * kRedPix;
+  if (bx < nimg) {
+    const int px0 = bx * kRedPix;
     const float t = need_h ? reduce_pixels16(E, NN, HG, px0, part, tid) : 0.f;
     if (tid < kRedPix) shared[px0 + tid] = t;
     return;
   }
   __shared__ double lanes[kRedThreads];
   reduce_scalars(E, M, NN, g_cx_e, g_cy_e, chi2_e, a, a_ref, shared, lanes, tid);
+}
+__global__ __launch_bounds__(kRedThreads) void joint_reduce_kernel(int E, int M, int NN, int need_h, const float *HG,
+                                                                    const float *g_cx_e, const float *g_cy_e,
+                                                                    const float *chi2_e, const float *a,
+                                                                    const float *a_ref, float *shared) {
+  joint_reduce_block((int)blockIdx.x, E, M, NN, need_h, HG, g_cx_e, g_cy_e, chi2_e, a, a_ref, shared);
 }
 
 // ---- kernel 3: regularisers, loss, AdaBelief -------------------------------------------------------
@@ -1843,8 +1866,10 @@ __device__ __forceinline__ float adabelief_step(float &p, float &m, float &s, fl
   return p;
 }
 
-template <int N, int PX>
-__global__ __launch_bounds__(N *N / PX) void joint_update_kernel(JointUpdArgs A) {
+// (Args: JointUpdArgs - the one-star kernel's own copy of its arguments, as it compiled before the batched form existed - or
+//  const JointUpdArgs & - a star's view read in place from device memory, without a private copy in scratch)
+template <int N, int PX, class Args>
+__device__ __forceinline__ void joint_update_body(Args A) {
   constexpr int NTHR = N * N / PX, NWV = (NTHR + 63) / 64, J = ilog2(N);
   extern __shared__ __align__(16) float lds[];
   __shared__ float red[NWV * 2 + 16];
@@ -2116,6 +2141,17 @@ __global__ __launch_bounds__(N *N / PX) void joint_update_kernel(JointUpdArgs A)
       if (A.out_loss) *A.out_loss = loss;
     }
   }
+}
+template <int N, int PX>
+__global__ __launch_bounds__(N *N / PX) void joint_update_kernel(JointUpdArgs A) {
+  joint_update_body<N, PX, JointUpdArgs>(A);
+}
+// Batched star photometry with a background grid per star (lc_joint_create_groups_background): workgroup g applies to star g
+// exactly what the one-workgroup launch above applies to a fit of that star alone, through the star's view (its h, W, scratch,
+// reduced block and regulariser outputs; uploaded by the host, read in place)
+template <int N, int PX>
+__global__ __launch_bounds__(N *N / PX) void joint_update_groups_uk_kernel(const JointUpdArgs *__restrict__ views) {
+  joint_update_body<N, PX, const JointUpdArgs &>(views[blockIdx.x]);
 }
 
 }  // namespace lc

@@ -80,11 +80,13 @@ class JointFit:
             keep = arrs
             cfg.n_prior = self.M
             cfg.prior_cx_mean, cfg.prior_cx_sigma, cfg.prior_cy_mean, cfg.prior_cy_sigma = [ptr(a) for a in arrs]
-        w = None
-        if W is not None:
-            w = f32(np.asarray(W)[:self.J].reshape(self.J, self.N, self.N))
+        w = None if W is None else self._weight_cube(W)
         self._keep = (keep, w)
         self._chk(self._l.lc_joint_set_loss(self.h, C.byref(cfg), ptr(w)), 'set_loss')
+
+    def _weight_cube(self, W):
+        """W as set_loss hands it to the device: the first J scales, float32."""
+        return f32(np.asarray(W)[:self.J].reshape(self.J, self.N, self.N))
 
     def propagate_noise(self):
         W = np.empty((self.J + 1, self.N, self.N), np.float32)
@@ -258,9 +260,14 @@ class StarPhotometryBatch(JointFit):
     device object (lc_joint_create_groups): ``stacks`` is a list of (data, sigma2, psf) per star, each over that star's
     own epochs ((E_g, n, n), (E_g, n, n), (E_g, N, N)); M point sources per star (1 in the reference).  Parameter arrays
     are the per-star arrays concatenated: a (sum E_g * M), c_x / c_y (G * M), dx / dy / mean (sum E_g).  Every AdaBelief
-    iteration is one kernel pair for all stars; each star's trajectory is bit for bit that of its own JointFit."""
+    iteration is one kernel pair for all stars; each star's trajectory is bit for bit that of its own JointFit.
 
-    def __init__(self, stacks, ss, M=1, ctx=None):
+    ``background=True`` (lc_joint_create_groups_background): every star also fits its own background grid under the starlet
+    regulariser.  Block h then has G * N * N entries, star-major (``split('h')``: one N * N array per star),
+    ``propagate_noise()`` returns (G, J + 1, N, N) and ``set_loss(W=...)`` takes that array (or its first J scales).  Stamp
+    sizes with a single-workgroup update only (n = 16, 24, 32 at ss = 2, n = 16 at ss = 1)."""
+
+    def __init__(self, stacks, ss, M=1, ctx=None, background=False):
         datas = [f32(d) for d, _, _ in stacks]
         sig2s = [f32(s2) for _, s2, _ in stacks]
         psfs = [f32(p) for _, _, p in stacks]
@@ -280,13 +287,30 @@ class StarPhotometryBatch(JointFit):
         self.J = int(np.log2(self.N))
         self.ctx = ctx or _lib.default_context()
         self._l = _lib.lib()
+        self.background = bool(background)
+        name = 'lc_joint_create_groups_background' if self.background else 'lc_joint_create_groups'
         h = C.c_void_p()
-        self.ctx.check(self._l.lc_joint_create_groups(self.ctx.h, self.G, self.epochs.ctypes.data_as(_lib.ip), self.M, self.n,
-                                                      self.ss, ptr(data), ptr(sig2), ptr(psf), C.byref(h)), 'lc_joint_create_groups')
+        self.ctx.check(getattr(self._l, name)(self.ctx.h, self.G, self.epochs.ctypes.data_as(_lib.ip), self.M, self.n, self.ss,
+                                              ptr(data), ptr(sig2), ptr(psf), C.byref(h)), name)
         self.h = h
         self.sizes = {'a': self.E * self.M, 'c_x': self.G * self.M, 'c_y': self.G * self.M, 'dx': self.E, 'dy': self.E,
-                      'alpha': self.E, 'h': self.N * self.N, 'mean': self.E}
+                      'alpha': self.E, 'h': (self.G if self.background else 1) * self.N * self.N, 'mean': self.E}
         self._keep = None
+
+    def _weight_cube(self, W):
+        if not self.background:
+            return super()._weight_cube(W)
+        W = np.asarray(W)
+        if W.ndim != 4 or W.shape[0] != self.G or W.shape[1] < self.J or W.shape[2:] != (self.N, self.N):
+            raise ValueError(f'W must be ({self.G}, J or J + 1, {self.N}, {self.N}) with J = {self.J}, got {W.shape}')
+        return f32(np.ascontiguousarray(W[:, :self.J]))
+
+    def propagate_noise(self):
+        if not self.background:
+            return super().propagate_noise()
+        W = np.empty((self.G, self.J + 1, self.N, self.N), np.float32)
+        self._chk(self._l.lc_joint_propagate_noise(self.h, ptr(W)), 'propagate_noise')
+        return W
 
     def loss_history(self):
         """(G, T + 1): per star, the loss before every update and the loss of the final parameters."""
@@ -300,8 +324,17 @@ class StarPhotometryBatch(JointFit):
         flat = np.asarray(flat)
         if name in ('c_x', 'c_y'):
             return [flat[g * self.M:(g + 1) * self.M] for g in range(self.G)]
+        if name == 'h' and self.background:
+            NN = self.N * self.N
+            return [flat[g * NN:(g + 1) * NN] for g in range(self.G)]
         k = self.M if name == 'a' else 1
         return [flat[self.starts[g] * k:self.starts[g + 1] * k] for g in range(self.G)]
+
+
+def background_batch_supported(n, ss):
+    """Whether StarPhotometryBatch(background=True) exists for n x n stamps at subsampling ss (the library decides:
+    lc_joint_groups_background_supported - the stamp sizes whose joint fit has a single-workgroup update)."""
+    return bool(_lib.lib().lc_joint_groups_background_supported(int(n), int(ss)))
 
 
 def joint_fit_size(n, ss):
@@ -324,6 +357,19 @@ def make_joint_fit(data, sigma2, psf, ss, M, ctx=None):
     if n_fit == n:
         return JointFit(data, sigma2, psf, ss, M, ctx)
     return EmbeddedJointFit(data, sigma2, psf, ss, M, ctx, n_fit)
+
+
+def ring_at_median_variance(var, sigma2, pad):
+    """The variances an embedded fit propagates its noise levels W from: ``var`` (E, n_fit, n_fit), the stamps' variances in the
+    centre, with the ring of width ``pad`` at each epoch's median of ``sigma2`` (E, n, n; float32) instead of the ring variance
+    (EmbeddedJointFit, and the batched star photometry at embedded sizes).  A new float32 array."""
+    out = np.array(var, dtype=np.float32)
+    E, n_fit = out.shape[0], out.shape[-1]
+    med = np.median(np.asarray(sigma2).reshape(E, -1), axis=1).astype(np.float32)
+    ring = np.ones((n_fit, n_fit), bool)
+    ring[pad:n_fit - pad, pad:n_fit - pad] = False
+    out[:, ring] = med[:, None]
+    return out
 
 
 class EmbeddedJointFit(JointFit):
@@ -361,11 +407,7 @@ class EmbeddedJointFit(JointFit):
         self._psf_fit = np.zeros((E, n_fit * ss, n_fit * ss), np.float32)
         self._psf_fit[:, P:P + n * ss, P:P + n * ss] = psf
         # (for the noise propagation: the ring at each epoch's median variance)
-        self._var_w = var.copy()
-        med = np.median(sigma2.reshape(E, -1), axis=1).astype(np.float32)
-        ring = np.ones((n_fit, n_fit), bool)
-        ring[p:p + n, p:p + n] = False
-        self._var_w[:, ring] = med[:, None]
+        self._var_w = ring_at_median_variance(var, sigma2, p)
         super().__init__(big, var, self._psf_fit, ss, M, ctx)
         self._dev_dims = (self.n, self.N, dict(self.sizes))
         self._user_dims = (n, n * ss, dict(self.sizes, h=(n * ss) ** 2))

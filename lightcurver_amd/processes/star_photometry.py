@@ -115,14 +115,18 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
     * both off (the pipeline's default): fluxes, the star's position and the per-epoch shifts free, no background - batched;
     * ``uniform_background_per_epoch=True``: the sky level of every epoch free as well - batched (one more per-epoch
       parameter of the same update);
-    * ``starlet_global_background=True``: every star its own background grid with the starlet regulariser.  The batched object
-      carries no background work space (no spectra, no slabs: lc_joint_create_groups), so these fits run one star after the
-      other through ``do_one_star_forward_modelling`` - same numbers, no batching gain.
+    * ``starlet_global_background=True``: every star its own background grid with the starlet regulariser (W propagated from
+      that star's noise maps, ``lam_scales = lam_hf = 3``) - batched as well (``StarPhotometryBatch(background=True)``,
+      lc_joint_create_groups_background) where the stamp size's joint fit has a single-workgroup update: n = 16, 24 (the
+      reference's default stamp_size_stars), 32 at subsampling 2 and n = 16 at 1, and the even sizes below 32 embedded in the
+      next of these as ``EmbeddedJointFit`` does it (h padded on the way in, cropped on the way out).  Larger stamps (40 - 128:
+      multi-block, cluster and matrix-core forms of the one-star fit) run one star after the other through
+      ``do_one_star_forward_modelling`` - same numbers, no batching gain.
 
     Returns one dictionary per star with ALL keys of ``do_one_star_forward_modelling`` (``deconvolved_image``: the scene of the
     star's first epoch, ``starlet_background``: zeros when no background is fitted - what the reference's caller reads at
     star_photometry.py:139-150); each star's numbers are bit for bit those of its own one-star fit."""
-    from ..joint import StarPhotometryBatch, EmbeddedJointFit, joint_fit_size
+    from ..joint import StarPhotometryBatch, EmbeddedJointFit, joint_fit_size, background_batch_supported
     from ..starred.deconvolution.deconvolution import nest_kwargs
     ss = int(subsampling_factor)
     if not stacks:
@@ -134,13 +138,13 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
     for d, nm, p in stacks:
         if np.asarray(nm).shape != np.asarray(d).shape or np.asarray(p).shape != (len(d), n_user * ss, n_user * ss):
             raise ValueError('every star needs data, noisemap (E_g, n, n) and psf (E_g, n ss, n ss)')
-    if starlet_global_background:
-        return [do_one_star_forward_modelling(d, nm, p, ss, n_iter=n_iter, uniform_background_per_epoch=uniform_background_per_epoch,
-                                              starlet_global_background=True) for d, nm, p in stacks]
     # a stamp size without a kernel of its own: the stamps in the centre of the next instantiated size, no weight on the ring
-    # (what joint.EmbeddedJointFit does for the one-star fit; no background here, so only the model has to be cut back)
+    # (what joint.EmbeddedJointFit does for the one-star fit: the model, and h where it is fitted, cut back to the caller's size)
     n_fit = joint_fit_size(n_user, ss)
     pad = (n_fit - n_user) // 2
+    if starlet_global_background and not background_batch_supported(n_fit, ss):
+        return [do_one_star_forward_modelling(d, nm, p, ss, n_iter=n_iter, uniform_background_per_epoch=uniform_background_per_epoch,
+                                              starlet_global_background=True) for d, nm, p in stacks]
 
     def embed(a, fill, f=1):
         if pad == 0:
@@ -158,28 +162,41 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
         scales.append(scale)
         guesses.append(np.nansum(data, axis=(1, 2)) - data[0].size * _border_level(data))
         dev_stacks.append((embed(data, 0.0), embed(noisemap ** 2, EmbeddedJointFit.RING_VARIANCE), embed(psf, 0.0, ss)))
-    batch = StarPhotometryBatch(dev_stacks, ss, M=1)
+    bg = bool(starlet_global_background)
+    batch = StarPhotometryBatch(dev_stacks, ss, M=1, background=bg)
     try:
         E, G, N = batch.E, batch.G, batch.N
+        W = (batch.propagate_noise() if pad == 0 else _embedded_noise_levels(stacks, dev_stacks, ss, pad)) if bg else None
         batch.set_params(a=np.concatenate(guesses), c_x=np.zeros(G), c_y=np.zeros(G), dx=np.zeros(E), dy=np.zeros(E),
-                         alpha=np.zeros(E), h=np.zeros(N * N), mean=np.zeros(E))
-        batch.set_loss(lam_scales=3.0, lam_hf=3.0)          # (constants with the background fixed at zero)
-        batch.set_free(['a', 'c_x', 'c_y', 'dx', 'dy'] + (['mean'] if uniform_background_per_epoch else []))
+                         alpha=np.zeros(E), h=np.zeros(batch.sizes['h']), mean=np.zeros(E))
+        # (the one-star function's Loss: starlet l1 at 3 / 3, positivity 0; without the background constants, h fixed at zero)
+        batch.set_loss(W=W, lam_scales=3.0, lam_hf=3.0)
+        batch.set_free(['a', 'c_x', 'c_y', 'dx', 'dy'] + (['h'] if bg else []) + (['mean'] if uniform_background_per_epoch else []))
         batch.run_adabelief(int(n_iter), init_learning_rate=1e-3, schedule_learning_rate=True)
         final = batch.get_params()
         hist = batch.loss_history()
+        P, Nu = pad * ss, n_user * ss
+        h_final = [hg.reshape(N, N)[P:P + Nu, P:P + Nu].ravel() for hg in batch.split(final['h'], 'h')] if bg else None
+        if bg and pad:
+            # the one-star function evaluates its model, uncertainties and scene from the caller-sized kwargs: h back on the
+            # device with its ring at zero (EmbeddedJointFit pads what it is given)
+            ring0 = np.zeros((G, N, N), np.float32)
+            ring0[:, P:P + Nu, P:P + Nu] = np.stack(h_final).reshape(G, Nu, Nu)
+            batch.set_params(h=ring0)
         model, _ = batch.model()
         model = model[:, pad:pad + n_user, pad:pad + n_user]
         sigma_a = batch.fisher_flux_sigma()
-        P, Nu = pad * ss, n_user * ss
-        scenes = [batch.deconvolved(int(batch.starts[g]))[0][P:P + Nu, P:P + Nu] for g in range(G)]
+        decon = [batch.deconvolved(int(batch.starts[g])) for g in range(G)]
+        scenes = [s[P:P + Nu, P:P + Nu] for s, _ in decon]
+        backgrounds = [b[P:P + Nu, P:P + Nu] for _, b in decon]
     finally:
         batch.close()
     out = []
     for g, (data, noisemap, psf) in enumerate(stacks):
         e0, e1 = batch.starts[g], batch.starts[g + 1]
+        h_g = np.ascontiguousarray(h_final[g]) if bg else np.zeros((n_user * ss) ** 2, np.float32)
         flat = dict(a=final['a'][e0:e1], c_x=final['c_x'][g:g + 1], c_y=final['c_y'][g:g + 1], dx=final['dx'][e0:e1],
-                    dy=final['dy'][e0:e1], alpha=final['alpha'][e0:e1], h=np.zeros((n_user * ss) ** 2, np.float32), mean=final['mean'][e0:e1])
+                    dy=final['dy'][e0:e1], alpha=final['alpha'][e0:e1], h=h_g, mean=final['mean'][e0:e1])
         k_final = nest_kwargs(flat)
         residuals = data - model[e0:e1]
         chi2_per_frame = np.nansum(residuals ** 2 / noisemap ** 2, axis=(1, 2)) / data.shape[1] ** 2
@@ -194,6 +211,19 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
             'loss_curve': np.asarray(hist[g, 1:], dtype=np.float64).tolist(),
             'residuals': scale * residuals,
             'deconvolved_image': scale * np.ascontiguousarray(scenes[g]),
-            'starlet_background': scale * np.zeros((n_user * ss, n_user * ss), np.float32),
+            'starlet_background': scale * (np.ascontiguousarray(backgrounds[g]) if bg else np.zeros((n_user * ss, n_user * ss), np.float32)),
         })
     return out
+
+
+def _embedded_noise_levels(stacks, dev_stacks, ss, pad):
+    """The starlet noise levels W of every star, (G, J + 1, N, N), of an embedded batch as EmbeddedJointFit.propagate_noise
+    has them: from a twin with zero data whose ring sits at each epoch's median variance."""
+    from ..joint import StarPhotometryBatch, ring_at_median_variance
+    twin = [(np.zeros(np.shape(d), np.float32), ring_at_median_variance(var, np.asarray(noisemap ** 2, dtype=np.float32), pad), p)
+            for (_, noisemap, _), (d, var, p) in zip(stacks, dev_stacks)]
+    b = StarPhotometryBatch(twin, ss, M=1, background=True)
+    try:
+        return b.propagate_noise()
+    finally:
+        b.close()

@@ -277,6 +277,15 @@ int lc_joint_create_groups_background(lc_ctx *ctx, int G, const int32_t *epochs_
 /* FisherCovariance(diagonal_only=True) with only `a` free -> sigma(a) [E*M]
  * (lightcurver/utilities/starred_utilities.py:36-38). */
 int lc_joint_fisher_flux_sigma(lc_joint *j, float *sigma_a);
+/* FisherCovariance(diagonal_only=False) with only `a` free: the full Fisher information of the fluxes.  The model is linear
+ * in a, so it is the exact Hessian of 1/2 chi2 (no regulariser: the flux-uniformity term would couple the epochs), independent
+ * of a and block diagonal over the epochs: F_e[i][j] = sum_pix w T_{e,i} T_{e,j} with T_{e,i} the unit-flux model of source i
+ * in epoch e.  Writes fisher = F and cov = F^-1 [E][M][M] and the marginal sigma = sqrt(diag cov) [E][M], epoch-major like a;
+ * each pointer may be null.  A source with F_ii = 0 (outside the stamp, or masked) has sigma = +inf and a zero row and column
+ * of cov, the rest of its epoch's block is solved without it; an epoch whose block is numerically singular (a Cholesky pivot
+ * not above 1e-6 times its diagonal entry) has NaN cov and sigma, the call still succeeds.  Same scope as
+ * lc_joint_fisher_flux_sigma (batched star photometry: every epoch with its own star), whose 1 / sqrt(F_ii) it matches. */
+int lc_joint_fisher_flux_cov(lc_joint *j, float *fisher, float *cov, float *sigma);
 /* Multi-GPU epoch sharding: split one optimiser step around the caller's all-reduce of the shared block
  * [dL/dh (N*N) | dL/dc_x (M) | dL/dc_y (M) | sum_e (a - ref) (M) | sum_e (a - ref)^2 (M) | chi2 | n_epochs]
  * living in device memory.  The flux moments (flux-uniformity term, jnp.std over epochs in the reference:

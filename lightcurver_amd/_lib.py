@@ -112,6 +112,7 @@ SIGNATURES = {
     'lc_joint_param_history_get': (C.c_int, [vp, C.c_int, C.c_int, fp]),
     'lc_joint_param_history_end': (C.c_int, [vp]),
     'lc_joint_fisher_flux_sigma': (C.c_int, [vp, fp]),
+    'lc_joint_fisher_flux_cov': (C.c_int, [vp, fp, fp, fp]),
     'lc_joint_step_local': (C.c_int, [vp]),
     'lc_joint_shared_buffer_dev': (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int)]),
     'lc_joint_step_update': (C.c_int, [vp, C.POINTER(AdabeliefCfg)]),

@@ -17,6 +17,7 @@
 #include "joint_ps.h"
 #include "joint_noise.h"
 #include "joint_lbfgs.h"
+#include "joint_fisher.h"
 #include "noise_host.h"
 #include "starlet_norms.h"
 
@@ -49,6 +50,8 @@ struct JointVariant {
   // its epoch's star (JointArgs::group) and the single-workgroup update over the stars' views
   epoch_fn ek_grp = nullptr;
   void (*uk_grp)(const JointUpdArgs *) = nullptr;
+  // the template mode (lc_joint_fisher_flux_cov): builds of ek (LDS e_lds) and ek_grp that also store the weighted templates
+  epoch_fn ek_tmpl = nullptr, ek_grp_tmpl = nullptr;
 };
 
 typedef void (*mreg_fn)(MregArgs);
@@ -173,6 +176,10 @@ struct lc_joint {
   float *phist = nullptr;
   int phist_cap = 0, phist_P = 0, phist_rows = 0, phist_off[LC_P_COUNT] = {};
   std::vector<float> h_sigma2, h_psf;  // host copies for the one-time noise propagation
+  // lc_joint_fisher_flux_cov (allocated on first use): the template slab [fcov_chunk][M][n*n] of one chunk of epochs, and
+  // F, C [E][M][M], sigma [E][M] one after the other
+  float *tmpl = nullptr, *fcov = nullptr;
+  int fcov_chunk = 0;
   std::vector<void *> allocs;
 };
 
@@ -202,9 +209,11 @@ JointVariant make_jv() {
   typedef JointCfg<N, SS, L, NW, false, LPF> C;
   JointVariant v{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, joint_update_kernel<N, PX>, N * N / PX,
                  (int)(StarletLds<N>::FLOATS * sizeof(float)), false, joint_epoch_kernel<C, true>};
+  v.ek_tmpl = joint_epoch_kernel<C, false, 0, false, true>;
   if constexpr (BG) {
     v.ek_grp = joint_epoch_kernel<C, false, 0, true>;
     v.uk_grp = joint_update_groups_uk_kernel<N, PX>;
+    v.ek_grp_tmpl = joint_epoch_kernel<C, false, 0, true, true>;
   }
   return v;
 }
@@ -225,7 +234,9 @@ JointVariant make_jv_cl() {
 template <int N, int SS, int L, int NW, int LPF = 16>
 JointVariant make_jv_plain() {
   typedef JointCfg<N, SS, L, NW, false, LPF> C;
-  return JointVariant{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, nullptr, 0, 0, false, joint_epoch_kernel<C, true>};
+  JointVariant v{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, nullptr, 0, 0, false, joint_epoch_kernel<C, true>};
+  v.ek_tmpl = joint_epoch_kernel<C, false, 0, false, true>;
+  return v;
 }
 // large grids: spectrum scratch in HBM, starlet / update as multi-block kernels
 template <int N, int SS, int L, int NW, int LPF = 16>
@@ -235,6 +246,7 @@ JointVariant make_jv_gm() {
   JointVariant v{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, nullptr, 0, 0, true, joint_epoch_kernel<C, true>,
                  joint_epoch_kernel<CT>, CT::LDS_BYTES};
   v.lpf = LPF;
+  v.ek_tmpl = joint_epoch_kernel<C, false, 0, false, true>;
   v.ek_phase[0] = joint_epoch_kernel<C, false, 1>;
   v.ek_phase[1] = joint_epoch_kernel<C, false, 2>;
   v.ek_phase[2] = joint_epoch_kernel<C, false, 3>;
@@ -349,12 +361,13 @@ bool reg_h_on(const lc_joint *j) {
 }
 
 typedef void (*ps_fn)(JointPsArgs);
-void find_ps_kernel(int N, int ss, ps_fn *fn, int *lds, bool persist = false) {
+// (tmpl: the template mode's build)
+void find_ps_kernel(int N, int ss, ps_fn *fn, int *lds, bool persist = false, bool tmpl = false) {
   *fn = nullptr;
-#define LC_PS(NN_, SS_)                                                                   \
-  if (N == NN_ && ss == SS_) {                                                            \
-    *fn = persist ? joint_ps_kernel<NN_, SS_, true> : joint_ps_kernel<NN_, SS_, false>;   \
-    *lds = joint_ps_lds_bytes<NN_, SS_>();                                                \
+#define LC_PS(NN_, SS_)                                                                                                 \
+  if (N == NN_ && ss == SS_) {                                                                                          \
+    *fn = persist ? joint_ps_kernel<NN_, SS_, true> : (tmpl ? joint_ps_kernel<NN_, SS_, false, true> : joint_ps_kernel<NN_, SS_, false>); \
+    *lds = joint_ps_lds_bytes<NN_, SS_>();                                                                              \
   }
   LC_PS(16, 1)
   LC_PS(32, 2)
@@ -396,8 +409,9 @@ int cluster_parts(const lc_joint *j) {
 }
 
 // (e0, e1, stream: the point-source-only kernel over the epochs [e0, e1) on `stream` - batched star photometry; default: all epochs)
+// (tmpl: mode 2 in template mode - JointArgs::tmpl - over the epochs [e0, e1), every kernel form that serves mode 2)
 int launch_epochs(lc_joint *j, int mode, int isrc, bool want_hgrad, float *model_out, int e0 = 0, int e1 = -1,
-                  hipStream_t ps_stream = nullptr) {
+                  hipStream_t ps_stream = nullptr, float *tmpl = nullptr) {
   const JointVariant *v = j->v;
   JointArgs A;
   std::memset(&A, 0, sizeof(A));
@@ -435,6 +449,7 @@ int launch_epochs(lc_joint *j, int mode, int isrc, bool want_hgrad, float *model
   A.group = j->group_dev;
   A.skip_D = (mode == 0 && j->fuse_stencil) ? 1 : 0;
   A.tshift = j->tshift;
+  A.tmpl = tmpl;
   // the LAST launch below carries the wait for this iteration's chain (one extra block), where one is due
   const bool carry_wait = j->epoch_wait_due && !ps_stream && mode == 0;
   j->epoch_wait_due = false;
@@ -454,7 +469,7 @@ int launch_epochs(lc_joint *j, int mode, int isrc, bool want_hgrad, float *model
   if (!A.h_active && j->M > 0 && j->psf_dev && !std::getenv("LCMI_JOINT_FFT_ONLY")) {
     ps_fn pk = nullptr;
     int plds = 0;
-    find_ps_kernel(j->N, j->ss, &pk, &plds);
+    find_ps_kernel(j->N, j->ss, &pk, &plds, false, tmpl != nullptr);
     if (pk) {
       if (!j->psF) {
         int rc = dmalloc(j, &j->psF, (size_t)j->E * j->M * 3 * j->n * j->n);
@@ -482,7 +497,7 @@ int launch_epochs(lc_joint *j, int mode, int isrc, bool want_hgrad, float *model
   if (j->bg) {  // one workgroup per epoch of [e0, e1), each with its star's h and positions (dynamic LDS set at create)
     if (e1 < 0) e1 = j->E;
     A.e_off = e0;
-    hipLaunchKernelGGL(v->ek_grp, dim3(e1 - e0), dim3(v->e_thr), v->e_lds, ps_stream ? ps_stream : j->ctx->stream, A);
+    hipLaunchKernelGGL(tmpl ? v->ek_grp_tmpl : v->ek_grp, dim3(e1 - e0), dim3(v->e_thr), v->e_lds, ps_stream ? ps_stream : j->ctx->stream, A);
     LC_HIP(j->ctx, hipGetLastError());
     return A.need_hgrad;
   }
@@ -543,11 +558,31 @@ int launch_epochs(lc_joint *j, int mode, int isrc, bool want_hgrad, float *model
     LC_HIP(j->ctx, hipGetLastError());
     return A.need_hgrad;
   }
-  epoch_fn ek = tile ? v->ek_tile : v->ek;
+  if (tmpl) tile = false;
+  epoch_fn ek = tmpl ? v->ek_tmpl : (tile ? v->ek_tile : v->ek);
   const int e_lds = tile ? v->e_lds_tile : v->e_lds;
+  int ne = j->E;
+  if (e0 != 0 || (e1 >= 0 && e1 != j->E)) {
+    // a range of the epochs (the template mode's chunks): the arrays of epoch e0 become those of the launch's first block.
+    // Mode 2 reads no other per-epoch array.
+    if (mode != 2) LC_FAIL(j->ctx, LC_ERR_INVALID, "launch_epochs: an epoch range is for the Fisher modes");
+    ne = e1 - e0;
+    const size_t nn = (size_t)j->n * j->n, MM = (size_t)j->M;
+    A.E = ne;
+    A.data += e0 * nn;
+    A.wgt += e0 * nn;
+    A.St += (size_t)e0 * j->KH * j->L;
+    if (A.spec) A.spec += (size_t)e0 * j->N * ((j->KH + 15) / 16 * 16);
+    A.a += e0 * MM;
+    A.alpha += e0;
+    A.dx += e0;
+    A.dy += e0;
+    A.mean += e0;
+    A.fisher_out += e0 * MM;
+  }
   LC_HIP(j->ctx, hipFuncSetAttribute((const void *)ek, hipFuncAttributeMaxDynamicSharedMemorySize, e_lds));
   if (carry_wait) attach_wait(j->E);
-  hipLaunchKernelGGL(ek, dim3(j->E + (carry_wait ? 1 : 0)), dim3(v->e_thr), e_lds, j->ctx->stream, A);
+  hipLaunchKernelGGL(ek, dim3(ne + (carry_wait ? 1 : 0)), dim3(v->e_thr), e_lds, j->ctx->stream, A);
   LC_HIP(j->ctx, hipGetLastError());
   return A.need_hgrad;
 }
@@ -1368,6 +1403,7 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
       TRY(dmalloc(j, &j->gstart_dev, G + 1));
       TRY(h2d(j, j->gstart_dev, j->gstart.data(), j->gstart.size() * sizeof(int)));
       LC_HIP(ctx, hipFuncSetAttribute((const void *)v->ek_grp, hipFuncAttributeMaxDynamicSharedMemorySize, v->e_lds));
+      LC_HIP(ctx, hipFuncSetAttribute((const void *)v->ek_grp_tmpl, hipFuncAttributeMaxDynamicSharedMemorySize, v->e_lds));
       LC_HIP(ctx, hipFuncSetAttribute((const void *)v->uk_grp, hipFuncAttributeMaxDynamicSharedMemorySize, v->u_lds));
     }
     TRY(dmalloc(j, &j->a_ref_g, (size_t)G * kMaxSources));
@@ -2805,6 +2841,40 @@ int lc_joint_fisher_flux_sigma(lc_joint *j, float *sigma_a) {
     if (rc < 0) return rc;
   }
   return d2h(j, sigma_a, j->fisher, (size_t)j->E * j->M * sizeof(float));
+}
+
+int lc_joint_fisher_flux_cov(lc_joint *j, float *fisher, float *cov, float *sigma) {
+  if (!j) return LC_ERR_INVALID;
+  LC_ENTER(j->ctx);
+  const int E = j->E, M = j->M, nn = j->n * j->n;
+  if (E == 0 || M == 0) return LC_OK;
+  if (!j->tmpl) {  // epochs per chunk: a slab of about 64 MiB
+    const size_t per = (size_t)M * nn * sizeof(float);
+    j->fcov_chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)E, ((size_t)64 << 20) / per));
+    int rc = dmalloc(j, &j->tmpl, (size_t)j->fcov_chunk * M * nn);
+    if (!rc) rc = dmalloc(j, &j->fcov, (size_t)E * M * (2 * M + 1));
+    if (rc) return rc;
+  }
+  float *F = j->fcov, *Cv = F + (size_t)E * M * M, *S = Cv + (size_t)E * M * M;
+  for (int e0 = 0; e0 < E; e0 += j->fcov_chunk) {
+    const int e1 = std::min(E, e0 + j->fcov_chunk);
+    for (int i = 0; i < M; ++i) {  // the slab is written whole: every pixel of every source of every epoch of the chunk
+      int rc = launch_epochs(j, 2, i, false, nullptr, e0, e1, nullptr, j->tmpl);
+      if (rc < 0) return rc;
+    }
+    FisherCovArgs G{j->tmpl, M, nn, F + (size_t)e0 * M * M, Cv + (size_t)e0 * M * M, S + (size_t)e0 * M};
+    hipLaunchKernelGGL(joint_fisher_cov_kernel, dim3(e1 - e0), dim3(kFisherThreads), 0, j->ctx->stream, G);
+    LC_HIP(j->ctx, hipGetLastError());
+  }
+  // (one copy back of the three outputs, which lie one after the other: each copy waits for the stream)
+  const size_t EMM = (size_t)E * M * M;
+  std::vector<float> host(2 * EMM + (size_t)E * M);
+  int rc = d2h(j, host.data(), F, host.size() * sizeof(float));
+  if (rc) return rc;
+  if (fisher) std::memcpy(fisher, host.data(), EMM * sizeof(float));
+  if (cov) std::memcpy(cov, host.data() + EMM, EMM * sizeof(float));
+  if (sigma) std::memcpy(sigma, host.data() + 2 * EMM, (size_t)E * M * sizeof(float));
+  return LC_OK;
 }
 
 #ifdef LC_STAMPS

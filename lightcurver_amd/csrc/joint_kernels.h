@@ -83,6 +83,9 @@ struct JointArgs {
   unsigned int *chain_err;
   int wait_block;
   int e_off;                  // GRP build: the first epoch of this launch (see `group`)
+  // template mode (mode 2 in the TMPL builds: lc_joint_fisher_flux_cov): also store sqrt(w) T_{e,isrc}, the weighted unit-flux
+  // model of source isrc, at tmpl[b][isrc][n][n] - b = blockIdx.x, the epoch's place in this launch
+  float *tmpl;
 };
 constexpr int kClStride = 32;    // flag words per epoch (one 128-byte line; kMaxParts <= 16 of them in use)
 constexpr int kClBarriers = 6;   // start | A | B | C | B' | C' | D: every cluster launch passes exactly six syncs
@@ -309,12 +312,15 @@ __device__ __forceinline__ void joint_epoch_totals(const JointArgs &A, int e, in
 // spectrum travels between the launches through global memory, and the launch boundaries are the synchronisation (no
 // waiting inside a kernel).  An epoch that would occupy one CU out of two then uses the whole machine, and every launch
 // holds the registers of one phase only.  The reductions of the epoch are finished by joint_epoch_finish_kernel.
-template <class C, bool AUX = false, int PHASE = 0, bool GRP = false>
+// TMPL: the template mode's build (JointArgs::tmpl), a compile-time variant of the one-workgroup kernel so that the stores cost
+// the other builds nothing.
+template <class C, bool AUX = false, int PHASE = 0, bool GRP = false, bool TMPL = false>
 // (Column phases built for two workgroups per CU - 128 registers, 31 to 74 of them spilled - measured slower than one at every
 //  split of the C5 shard: 367 - 405 us per iteration against 338.)
 __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
   static_assert(PHASE == 0 || (C::GSPEC && !AUX), "one phase per launch: spectrum in global memory");
   static_assert(!GRP || (PHASE == 0 && !AUX), "per-star background: the one-workgroup kernel");
+  static_assert(!TMPL || (PHASE == 0 && !AUX), "template mode: the one-workgroup kernel");
   if (A.upd_signal && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)   // (JointArgs: the update before this launch is complete)
     __hip_atomic_store(A.upd_signal, A.upd_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (A.chain_flag && (int)blockIdx.x == A.wait_block) {   // (JointArgs: the extra block that waits for the regulariser chain)
@@ -1111,6 +1117,11 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
           if (A.mode == 2) {
             acc_fis = fmaf(w0 * y.x, y.x, acc_fis);
             acc_fis = fmaf(w1 * y.y, y.y, acc_fis);
+            if constexpr (TMPL) {
+              float *Te = A.tmpl + ((size_t)blockIdx.x * M + A.isrc) * (n * n);
+              Te[I0 * n + jd] = sqrtf(w0) * y.x;
+              Te[I1 * n + jd] = sqrtf(w1) * y.y;
+            }
           } else {
             const float m0 = y.x + meane, m1 = y.y + meane;
             const float r0 = m0 - pd0[n2 < NDH ? n2 : 0], r1 = m1 - pd1[n2 < NDH ? n2 : 0];
@@ -1183,6 +1194,7 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
           const float w = we[I * n + jd];
           if (A.mode == 2) {
             acc_fis = fmaf(w * conv, conv, acc_fis);
+            if constexpr (TMPL) A.tmpl[((size_t)blockIdx.x * M + A.isrc) * (n * n) + I * n + jd] = sqrtf(w) * conv;
           } else {
             const float model = conv + meane;
             const float res = model - de[I * n + jd];
@@ -1198,6 +1210,11 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
           if (A.mode == 2) {
             acc_fis = fmaf(w0 * y.x, y.x, acc_fis);
             acc_fis = fmaf(w1 * y.y, y.y, acc_fis);
+            if constexpr (TMPL) {
+              float *Te = A.tmpl + ((size_t)blockIdx.x * M + A.isrc) * (n * n);
+              Te[u0 * n + jd] = sqrtf(w0) * y.x;
+              Te[(u0 + 1) * n + jd] = sqrtf(w1) * y.y;
+            }
           } else {
             const float m0 = y.x + meane, m1 = y.y + meane;
             const float r0 = m0 - de[u0 * n + jd], r1 = m1 - de[(u0 + 1) * n + jd];

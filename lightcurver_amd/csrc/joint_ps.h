@@ -65,7 +65,8 @@ struct JointPsArgs {
 // optimisation loop runs inside this kernel: the PSF tile stays in LDS, the parameters and their AdaBelief moments in
 // LDS / registers, and the loss history leaves as one value per epoch and iteration (summed over the epochs afterwards).
 // Same arithmetic per iteration as the launch-per-iteration form (same filters, same reductions, same update).
-template <int N, int SS, bool PERSIST = false>
+// TMPL: the template mode's build (JointArgs::tmpl; not with PERSIST).
+template <int N, int SS, bool PERSIST = false, bool TMPL = false>
 __global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <= 64 && !PERSIST) ? 4 : 1, (N <= 64 && !PERSIST) ? 4 : 8))) void joint_ps_kernel(JointPsArgs P) {
   constexpr int n = N / SS, NT = ntaps(SS), TS = N + 1, RS = n + 1, nn = n * n, NWV = kPsThreads / 64;
   constexpr int NQ = 4 + 3 * kMaxSources;
@@ -235,6 +236,7 @@ __global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <
         const float w = we[px], fv = fvr[t][jj];
         if (A.mode == 2) {
           vals[0] = fmaf(w * fv, fv, vals[0]);
+          if constexpr (TMPL) A.tmpl[((size_t)blockIdx.x * M + A.isrc) * nn + px] = sqrtf(w) * fv;
           continue;
         }
         const float model = fmaf(a0f, fv, meane);
@@ -255,6 +257,7 @@ __global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <
     if (A.mode == 2) {
       const float fv = Fe[((size_t)A.isrc * 3) * nn + px];
       vals[0] = fmaf(w * fv, fv, vals[0]);
+      if constexpr (TMPL) A.tmpl[((size_t)blockIdx.x * M + A.isrc) * nn + px] = sqrtf(w) * fv;
       continue;
     }
     float model = meane;

@@ -204,6 +204,18 @@ class JointFit:
         self._chk(self._l.lc_joint_fisher_flux_sigma(self.h, ptr(s)), 'fisher_flux_sigma')
         return s
 
+    def fisher_flux_covariance(self):
+        """Full Fisher information of the fluxes with everything else fixed (lc_joint_fisher_flux_cov): (F, C, sigma), F and its
+        inverse C as (E, M, M) blocks - the information is block diagonal over the epochs - and the marginal 1-sigma
+        sqrt(diag C) as (E * M,), epoch-major like ``a``.  fisher_flux_sigma() is 1 / sqrt(diag F), the error of one flux with
+        the others held fixed.  A source with F_ii = 0 has sigma = inf and a zero row / column of C; an epoch whose block is
+        numerically singular has NaN in C and sigma."""
+        F = np.empty((self.E, self.M, self.M), np.float32)
+        Cv = np.empty((self.E, self.M, self.M), np.float32)
+        s = np.empty(self.E * self.M, np.float32)
+        self._chk(self._l.lc_joint_fisher_flux_cov(self.h, ptr(F), ptr(Cv), ptr(s)), 'fisher_flux_cov')
+        return F, Cv, s
+
     # multi-GPU split step (epoch sharding)
     def step_local(self):
         self._chk(self._l.lc_joint_step_local(self.h), 'step_local')

@@ -137,7 +137,8 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
 
 def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pixels, initial_a, scale,
                               group=None, use_peer=False, regularization=None, roi_deconv_translations_iters=300,
-                              roi_deconv_all_iters=2000, further_optimize_background=True, ctx=None):
+                              roi_deconv_all_iters=2000, further_optimize_background=True, ctx=None,
+                              return_flux_covariance=False):
     """The two-stage fit of ``model_roi_cutouts`` with the epochs spread over the ranks of a torch.distributed group (one
     process per GPU): every rank passes ITS epochs - data, noisemap (E_local, n, n), psf (E_local, N, N) - and the same
     ``initial_a`` (M fluxes) and ``scale`` (nanmax of the data of ALL epochs: ``global_scale``).  The reference has no
@@ -148,7 +149,9 @@ def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels
     noise propagation: every rank its epochs, the levels added in quadrature over the ranks; stage 2: AdaBelief on everything
     but the rotation (``ShardedJointOptimizer.run``: the loop in C++, one all-reduce of the shared block per iteration,
     ``use_peer``: by the one-shot peer-memory kernel).  Returns, on every rank, the parameters of ALL epochs (gathered), the
-    loss histories and the Fisher 1-sigma of the fluxes at the final point."""
+    loss histories and the Fisher 1-sigma of the fluxes at the final point.  ``return_flux_covariance``: also the (E, M, M)
+    covariance blocks of the fluxes of all epochs (``fluxes_covariance``: every rank its epochs', gathered in the order of
+    ``fluxes_sigma``)."""
     import torch
     import torch.distributed as dist
     from ..distributed import PeerGroup, ShardedJointOptimizer, gather_epoch_blocks, host_group
@@ -194,15 +197,20 @@ def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels
         fit.ctx.synchronize()
         final = gather_epoch_blocks(fit.get_params(), M, group)
         sigma_loc = np.asarray(fit.fisher_flux_sigma(), np.float64)
+        cov_loc = np.asarray(fit.fisher_flux_covariance()[1], np.float64) if return_flux_covariance else None
         if dist.is_initialized() and dist.get_world_size(group) > 1:
             parts = [None] * dist.get_world_size(group)
-            dist.all_gather_object(parts, sigma_loc, group=host_group(group))
-            sigma = np.concatenate(parts)
+            dist.all_gather_object(parts, (sigma_loc, cov_loc), group=host_group(group))
+            sigma = np.concatenate([s for s, _ in parts])
+            cov = np.concatenate([c for _, c in parts]) if return_flux_covariance else None
         else:
-            sigma = sigma_loc
+            sigma, cov = sigma_loc, cov_loc
         # (the entry lc_joint_get_loss_history appends for the final parameters is a local evaluation: dropped)
-        return dict(flat_final=final, loss_history=np.asarray(fit.loss_history(), np.float64)[:-1], loss_history_stage1=hist1,
-                    fluxes_sigma=sigma, scale=scale, W=W)
+        out = dict(flat_final=final, loss_history=np.asarray(fit.loss_history(), np.float64)[:-1], loss_history_stage1=hist1,
+                   fluxes_sigma=sigma, scale=scale, W=W)
+        if return_flux_covariance:
+            out['fluxes_covariance'] = cov
+        return out
     finally:
         # (errors of the sharded stages are agreed over the ranks before they are raised - distributed.raise_together - so every
         #  rank arrives here, and the bounded host barrier inside peer.close() finds its partners)

@@ -1,0 +1,39 @@
+"""Ad-hoc timing of the flux errors: the diagonal Fisher call (fisher_flux_sigma, M epoch launches) against the full Fisher
+information (fisher_flux_covariance: the same M launches writing the template slab, the Gram-and-solve kernel, three copies
+back).  python tools/fisher_speed.py [reps] - at the C4 size (200 epochs of 64 x 64, M = 4) and one C5 shard (125 epochs of
+128 x 128, M = 8), background non-zero (the FFT epoch kernels) and zero (the point-source kernel where the size has one)."""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+from lightcurver_amd import _lib
+from lightcurver_amd.joint import JointFit
+from lightcurver_amd.synthetic import make_roi_dataset
+
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+ctx = _lib.Context(0)
+for name, E, n, M in (('C4', 200, 64, 4), ('C5-shard', 125, 128, 8)):
+    ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=11, with_background=True)
+    p = {k: np.asarray(v, np.float64) for k, v in ds['truth'].items()}
+    for bg in (True, False):
+        q = dict(p) if bg else dict(p, h=np.zeros_like(p['h']))
+        j = JointFit(ds['data'], ds['noisemap'].astype(np.float64) ** 2, ds['psf'], 2, M, ctx)
+        j.set_params(**q)
+        j.set_free(['a'])
+        j.fisher_flux_sigma()
+        j.fisher_flux_covariance()   # (first call: the template slab is allocated)
+        ctx.synchronize()
+        res = {}
+        for label, fn in (('diagonal', j.fisher_flux_sigma), ('covariance', j.fisher_flux_covariance)):
+            t = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                t.append(time.perf_counter() - t0)
+            res[label] = float(np.median(t)) * 1e3
+        j.close()
+        print(f'{name} E={E} n={n} M={M} background={"on " if bg else "off"}: diagonal {res["diagonal"]:.3f} ms, '
+              f'covariance {res["covariance"]:.3f} ms, ratio {res["covariance"] / res["diagonal"]:.2f}', flush=True)

@@ -77,6 +77,29 @@ int lc_prepare_stamps(lc_ctx *ctx, int K, int npix, const float *data, const flo
                       float noise_boost, int boost_whole_stamp, float *data_out, float *noisemap_out,
                       float *weight_out, int32_t *masked_count, float *kernel_ms);
 
+/* ---- cosmic-ray mask of the stamps: replaces astroscrappy.detect_cosmics ----------------------
+ * Reference call site: lightcurver/processes/cutout_making.py:85 (once per stamp, from :194 for the ROI and :247 for each
+ * star), with the arguments of config.yaml:209-214.  L.A.Cosmic as frozen in DESIGN.md §5 "Cosmic-ray detection": every
+ * float32 operation fixed, so one call over K stamps gives the bits of the SPEC's float32 restatement.
+ *   data [K][n][n]; invar [K][n][n] variance (the reference passes noisemap^2) or NULL (noise from the median-filtered
+ *   data and readnoise); inmask [K][n][n] (1 = bad) or NULL.  Non-finite data or invar and invar <= 0 are masked, C = 0.
+ *   crmask [K][n][n] (1 = cosmic); clean [K][n][n] the meanmask-cleaned stamp / gain; iters [K] iterations done (the loop
+ *   stops after the first one that adds nothing); kernel_ms = device time of the kernel (HIP events).
+ * Any square n from 8 to 128 (lc_cosmics_supported, no device needed; LC_ERR_UNSUPPORTED otherwise), any K, one launch.
+ * cleantype / fsmode other than 0 (astroscrappy's 'meanmask' / 'median') return LC_ERR_UNSUPPORTED. */
+typedef struct {
+  float sigclip, sigfrac, objlim; /* 4.5, 0.3, 5.0 */
+  float gain, readnoise, satlevel; /* 1.0, 6.5, 65536.0 */
+  int32_t niter;                   /* 4 */
+  int32_t sepmed;                  /* 1: separable medians (7, 5, 9); 0: full (5, 3, 7) */
+  int32_t cleantype;               /* 0 = meanmask (the only one built) */
+  int32_t fsmode;                  /* 0 = median (the only one built) */
+} lc_cosmics_cfg;
+int lc_cosmics_supported(int n);
+int lc_detect_cosmics(lc_ctx *ctx, int K, int n, const float *data, const float *invar /*nullable*/,
+                      const uint8_t *inmask /*nullable*/, const lc_cosmics_cfg *cfg, uint8_t *crmask,
+                      float *clean /*nullable*/, int32_t *iters /*nullable*/, float *kernel_ms /*nullable*/);
+
 /* ---- optimiser settings shared by both fits ----------------------------------------------- */
 /* optax.adabelief as driven by STARRED's Optimizer(method='adabelief'):
  * lightcurver/processes/star_photometry.py:113-122, roi_modelling.py:326-334. */

@@ -40,6 +40,12 @@ class JointLossCfg(C.Structure):
                 ('prior_cx_mean', fp), ('prior_cx_sigma', fp), ('prior_cy_mean', fp), ('prior_cy_sigma', fp)]
 
 
+class CosmicsCfg(C.Structure):
+    _fields_ = [('sigclip', C.c_float), ('sigfrac', C.c_float), ('objlim', C.c_float), ('gain', C.c_float),
+                ('readnoise', C.c_float), ('satlevel', C.c_float), ('niter', C.c_int32), ('sepmed', C.c_int32),
+                ('cleantype', C.c_int32), ('fsmode', C.c_int32)]
+
+
 # every symbol include/lcmi.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     'lc_version': (C.c_int, []),
@@ -50,6 +56,9 @@ SIGNATURES = {
     'lc_ctx_marker': (C.c_int, [vp, C.c_int]),
     'lc_prepare_stamps': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp, C.POINTER(C.c_uint8), C.c_float, C.c_float,
                                     C.c_int, fp, fp, fp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    'lc_cosmics_supported': (C.c_int, [C.c_int]),
+    'lc_detect_cosmics': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_uint8), C.POINTER(CosmicsCfg),
+                                    C.POINTER(C.c_uint8), fp, ip, C.POINTER(C.c_float)]),
     'lc_ctx_stream': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     'lc_ctx_synchronize': (C.c_int, [vp]),
     'lc_timer_start': (C.c_int, [vp]),

@@ -1,0 +1,389 @@
+// Cosmic-ray detection on star and ROI stamps: L.A.Cosmic (van Dokkum 2001) as astroscrappy's detect_cosmics applies it
+// with the reference's arguments (lightcurver/processes/cutout_making.py:85, config.yaml:209-214), frozen as the SPEC of
+// DESIGN.md §5 "Cosmic-ray detection".  Every float32 operation is the SPEC's, in its order; the medians select values,
+// so the result is bit for bit that of the SPEC's NumPy float32 restatement (tests/_lacosmic.py).
+//
+// One workgroup per stamp, every niter iteration inside the launch, the early exit a workgroup-wide vote.  The stamp's
+// planes (C, N, SP, F, two temporaries, four byte masks: 28 n^2 bytes) live in LDS up to n = 64 (112 KiB) and in a
+// global scratch slab per workgroup above that (the grid then strides over the stamps).  Separable medians of 5, 7 and
+// 9 values are sorted in registers by transposition networks; the 9-, 25- and 49-value medians of sepmed = 0 are
+// counting selections over the window.
+#pragma clang fp contract(off)  // the SPEC fixes every rounding: no fused multiply-adds, on the device or the host
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "lc_common.h"
+#include "../../include/lcmi.h"
+
+namespace lc {
+
+constexpr int kCrThreads = 256;
+constexpr int kCrMinN = 8, kCrMaxN = 128, kCrLdsMaxN = 64;
+constexpr int kCrFloatPlanes = 6, kCrBytePlanes = 4;
+
+__host__ __device__ constexpr size_t cr_plane_bytes(int n) {
+  return (size_t)n * n * (4 * kCrFloatPlanes + kCrBytePlanes);
+}
+
+struct CrArgs {
+  int K, n, niter, sepmed, have_invar;
+  const float *data, *invar;
+  const uint8_t *inmask;
+  uint8_t *crmask;
+  float *clean;
+  int *iters;
+  float *scratch;       // global planes (n > kCrLdsMaxN): gridDim.x slabs of cr_plane_bytes(n)
+  float gain, gain2;    // gain, gain * gain
+  float rn2, vhole;     // readnoise^2, 1e-5 + readnoise^2 (the variance the NaN rule gives a hole)
+  float satg, satg10;   // gain * satlevel, (gain * satlevel) / 10
+  float sigclip, sigcliplow, objlim;  // sigcliplow = sigfrac * sigclip
+};
+
+template <int K>
+__device__ __forceinline__ float median_net(float (&v)[K]) {
+#pragma unroll
+  for (int pass = 0; pass < K; ++pass) {
+#pragma unroll
+    for (int i = pass & 1; i + 1 < K; i += 2) {
+      const float a = v[i], b = v[i + 1];
+      v[i] = fminf(a, b);
+      v[i + 1] = fmaxf(a, b);
+    }
+  }
+  return v[K / 2];
+}
+
+// one pass of a separable median: 1 x K along rows (stride 1) or K x 1 along columns (stride n)
+template <int K, bool kRows>
+__device__ __forceinline__ void med_pass(const float *X, float *Y, int n) {
+  constexpr int h = K / 2;
+  const int np = n * n;
+  for (int p = threadIdx.x; p < np; p += kCrThreads) {
+    const int i = p / n, j = p - i * n;
+    const int c = kRows ? j : i;
+    if (c < h || c >= n - h) {
+      Y[p] = X[p];
+    } else {
+      constexpr int s0 = -h;
+      float v[K];
+#pragma unroll
+      for (int t = 0; t < K; ++t) v[t] = X[p + (s0 + t) * (kRows ? 1 : n)];
+      Y[p] = median_net<K>(v);
+    }
+  }
+}
+
+// full k x k median by counting selection (rank (k*k)/2): the sepmed = 0 path, correct rather than fast
+__device__ __forceinline__ void med_full(const float *X, float *Y, int n, int k) {
+  const int h = k / 2, np = n * n, r = (k * k) / 2;
+  for (int p = threadIdx.x; p < np; p += kCrThreads) {
+    const int i = p / n, j = p - i * n;
+    if (i < h || i >= n - h || j < h || j >= n - h) {
+      Y[p] = X[p];
+      continue;
+    }
+    float out = X[p];
+    for (int a = 0; a < k * k; ++a) {
+      const float va = X[(i - h + a / k) * n + (j - h + a % k)];
+      int less = 0, le = 0;
+      for (int b = 0; b < k * k; ++b) {
+        const float vb = X[(i - h + b / k) * n + (j - h + b % k)];
+        less += vb < va;
+        le += vb <= va;
+      }
+      if (less <= r && r < le) {
+        out = va;
+        break;
+      }
+    }
+    Y[p] = out;
+  }
+}
+
+// Y = median of X: sepmed -> 1 x k then k x 1 (T is the row pass's output), else the full k_full x k_full median
+template <int KS>
+__device__ __forceinline__ void median(bool sepmed, int k_full, const float *X, float *T, float *Y, int n) {
+  if (sepmed) {
+    med_pass<KS, true>(X, T, n);
+    __syncthreads();
+    med_pass<KS, false>(T, Y, n);
+  } else {
+    med_full(X, Y, n, k_full);
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ bool dil3_at(const uint8_t *B, int i, int j, int n) {
+  bool r = false;
+  for (int y = max(i - 1, 0); y <= min(i + 1, n - 1); ++y)
+    for (int x = max(j - 1, 0); x <= min(j + 1, n - 1); ++x) r |= B[y * n + x] != 0;
+  return r;
+}
+
+__device__ __forceinline__ float clip0(float v) { return v < 0.f ? 0.f : v; }
+
+// step 2a at pixel (i, j): the four sub-pixels of its 2 x 2 block on the subsampled grid, ring of that grid = 0
+__device__ __forceinline__ float laplace_rebin(const float *C, int i, int j, int n) {
+  const int p = i * n + j;
+  const float c = C[p], c4 = 4.0f * c;
+  const bool top = i == 0, bottom = i == n - 1, left = j == 0, right = j == n - 1;
+  const float up = top ? 0.f : C[p - n], down = bottom ? 0.f : C[p + n];
+  const float lf = left ? 0.f : C[p - 1], rt = right ? 0.f : C[p + 1];
+  const float tl = (top || left) ? 0.f : clip0(c4 - (((up + c) + lf) + c));
+  const float tr = (top || right) ? 0.f : clip0(c4 - (((up + c) + c) + rt));
+  const float bl = (bottom || left) ? 0.f : clip0(c4 - (((c + down) + lf) + c));
+  const float br = (bottom || right) ? 0.f : clip0(c4 - (((c + down) + c) + rt));
+  return ((tl + tr) + (bl + br)) * 0.25f;
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
+  extern __shared__ __align__(16) float cr_lds[];
+  __shared__ int s_cnt[kCrThreads / 64];
+  __shared__ float s_fallback;
+  const int n = A.n, np = n * n, tid = threadIdx.x;
+  const bool sepmed = A.sepmed != 0;
+  float *base = kLds ? cr_lds : A.scratch + (size_t)blockIdx.x * (cr_plane_bytes(n) / 4);
+  float *C = base, *Np = C + np, *S = Np + np, *T1 = S + np, *T2 = T1 + np, *Fp = T2 + np;
+  uint8_t *M = (uint8_t *)(Fp + np), *CR = M + np, *B1 = CR + np, *B2 = B1 + np;
+
+  for (int k = blockIdx.x; k < A.K; k += gridDim.x) {
+    const size_t off = (size_t)k * np;
+    // 0: C = gain D, V = invar gain^2, mask = inmask + the NaN rule
+    for (int p = tid; p < np; p += kCrThreads) {
+      const float d = A.data[off + p];
+      float c = A.gain * d;
+      bool hole = !__builtin_isfinite(d);
+      float v = 0.f;
+      if (A.have_invar) {
+        const float iv = A.invar[off + p];
+        hole = hole || !__builtin_isfinite(iv) || iv <= 0.f;
+        v = iv * A.gain2;
+      }
+      if (hole) {
+        c = 0.f;
+        v = A.vhole;
+      }
+      C[p] = c;
+      if (A.have_invar) Np[p] = sqrtf(v);
+      M[p] = (hole || (A.inmask && A.inmask[off + p] != 0)) ? 1 : 0;
+      CR[p] = 0;
+    }
+    __syncthreads();
+    // 1: saturated pixels, grown by two 3 x 3 dilations
+    median<7>(sepmed, 5, C, T1, T2, n);
+    for (int p = tid; p < np; p += kCrThreads) B1[p] = (C[p] >= A.satg && T2[p] > A.satg10) ? 1 : 0;
+    __syncthreads();
+    for (int p = tid; p < np; p += kCrThreads) B2[p] = dil3_at(B1, p / n, p % n, n) ? 1 : 0;
+    __syncthreads();
+    for (int p = tid; p < np; p += kCrThreads) M[p] |= dil3_at(B2, p / n, p % n, n) ? 1 : 0;
+    __syncthreads();
+
+    int done = 0;
+    for (int it = 0; it < A.niter; ++it) {
+      done = it + 1;
+      // b: noise model without invar
+      if (!A.have_invar) {
+        median<7>(sepmed, 5, C, T1, T2, n);
+        for (int p = tid; p < np; p += kCrThreads) Np[p] = sqrtf(fmaxf(T2[p], 1e-5f) + A.rn2);
+        __syncthreads();
+      }
+      // a, c: S = L / (2 N), SP = S - m5(S)
+      for (int p = tid; p < np; p += kCrThreads) {
+        const int i = p / n, j = p - i * n;
+        S[p] = laplace_rebin(C, i, j, n) / (2.0f * Np[p]);
+      }
+      __syncthreads();
+      median<7>(sepmed, 5, S, T1, T2, n);
+      for (int p = tid; p < np; p += kCrThreads) S[p] = S[p] - T2[p];
+      // d: fine structure F = max((m3 - m7(m3)) / N, 0.01)
+      median<5>(sepmed, 3, C, T1, Fp, n);
+      median<9>(sepmed, 7, Fp, T1, T2, n);
+      for (int p = tid; p < np; p += kCrThreads) Fp[p] = fmaxf((Fp[p] - T2[p]) / Np[p], 0.01f);
+      __syncthreads();
+      // e, f: candidates and their growth
+      for (int p = tid; p < np; p += kCrThreads) {
+        const float sp = S[p];
+        B1[p] = (sp > A.sigclip && !M[p] && sp / Fp[p] > A.objlim) ? 1 : 0;
+      }
+      __syncthreads();
+      for (int p = tid; p < np; p += kCrThreads)
+        B2[p] = (dil3_at(B1, p / n, p % n, n) && S[p] > A.sigclip && !M[p]) ? 1 : 0;
+      __syncthreads();
+      // g: CR |= g2; stop when g2 is empty
+      int any = 0;
+      for (int p = tid; p < np; p += kCrThreads) {
+        if (dil3_at(B2, p / n, p % n, n) && S[p] > A.sigcliplow && !M[p]) {
+          CR[p] = 1;
+          any = 1;
+        }
+      }
+      if (!__syncthreads_or(any)) break;
+      // h: meanmask from the C of before this step; T1 = replacement, B1 = no good pixel in the window
+      int need = 0;
+      for (int p = tid; p < np; p += kCrThreads) {
+        if (!CR[p]) continue;
+        const int i = p / n, j = p - i * n;
+        float acc = 0.f;
+        int cnt = 0;
+        for (int y = max(i - 2, 0); y <= min(i + 2, n - 1); ++y)
+          for (int x = max(j - 2, 0); x <= min(j + 2, n - 1); ++x) {
+            const int q = y * n + x;
+            if (!CR[q] && !M[q]) {
+              acc = acc + C[q];
+              ++cnt;
+            }
+          }
+        B1[p] = cnt == 0 ? 1 : 0;
+        if (cnt) T1[p] = acc / (float)cnt;
+        need |= cnt == 0;
+      }
+      if (__syncthreads_or(need)) {
+        // lower median (rank (m - 1) / 2) of the good pixels of the stamp, by counting; 0 when there are none
+        int m = 0;
+        for (int p = tid; p < np; p += kCrThreads) m += (!CR[p] && !M[p]) ? 1 : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m += __shfl_down(m, o, 64);
+        if ((tid & 63) == 0) s_cnt[tid >> 6] = m;
+        if (tid == 0) s_fallback = 0.f;
+        __syncthreads();
+        m = 0;
+        for (int w = 0; w < kCrThreads / 64; ++w) m += s_cnt[w];
+        const int r = (m - 1) / 2;
+        for (int p = tid; p < np && m > 0; p += kCrThreads) {
+          if (CR[p] || M[p]) continue;
+          const float va = C[p];
+          int less = 0, le = 0;
+          for (int q = 0; q < np; ++q) {
+            if (CR[q] || M[q]) continue;
+            less += C[q] < va;
+            le += C[q] <= va;
+          }
+          if (less <= r && r < le) s_fallback = va;  // every writer holds the same value
+        }
+        __syncthreads();
+      }
+      for (int p = tid; p < np; p += kCrThreads)
+        if (CR[p]) C[p] = B1[p] ? s_fallback : T1[p];
+      __syncthreads();
+    }
+    for (int p = tid; p < np; p += kCrThreads) {
+      A.crmask[off + p] = CR[p];
+      if (A.clean) A.clean[off + p] = C[p] / A.gain;
+    }
+    if (tid == 0 && A.iters) A.iters[k] = done;
+    __syncthreads();  // the planes are reused by the next stamp of this workgroup
+  }
+}
+
+}  // namespace lc
+
+using namespace lc;
+
+extern "C" {
+
+int lc_cosmics_supported(int n) { return n >= kCrMinN && n <= kCrMaxN ? 1 : 0; }
+
+int lc_detect_cosmics(lc_ctx *ctx, int K, int n, const float *data, const float *invar, const uint8_t *inmask,
+                      const lc_cosmics_cfg *cfg, uint8_t *crmask, float *clean, int32_t *iters, float *kernel_ms) {
+  if (!ctx) return LC_ERR_INVALID;
+  if (K <= 0 || !data || !cfg || !crmask) LC_FAIL(ctx, LC_ERR_INVALID, "lc_detect_cosmics: invalid argument");
+  if (!lc_cosmics_supported(n))
+    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_detect_cosmics: stamp size outside 8 .. 128");
+  if (cfg->cleantype != 0 || cfg->fsmode != 0)
+    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_detect_cosmics: only cleantype = meanmask and fsmode = median are built");
+  if (!(cfg->gain > 0.f) || !std::isfinite(cfg->gain) || !std::isfinite(cfg->readnoise) ||
+      !std::isfinite(cfg->sigclip) || !std::isfinite(cfg->sigfrac) || !std::isfinite(cfg->objlim) ||
+      std::isnan(cfg->satlevel) || cfg->niter < 0)
+    LC_FAIL(ctx, LC_ERR_INVALID, "lc_detect_cosmics: invalid settings");
+  LC_ENTER(ctx);
+  const size_t np = (size_t)n * n, tot = (size_t)K * np;
+  const bool lds = n <= kCrLdsMaxN;
+  const int grid = lds ? K : std::min(K, std::max(ctx->n_cu, 1) * 2);
+  std::vector<void *> dev;
+  auto cleanup = [&]() {
+    for (void *p : dev) (void)hipFree(p);
+  };
+  auto alloc = [&](size_t bytes, void **d) -> hipError_t {
+    hipError_t e = hipMalloc(d, bytes);
+    if (e == hipSuccess) dev.push_back(*d);
+    return e;
+  };
+#define CR_TRY(call)                                              \
+  do {                                                            \
+    hipError_t e_ = (call);                                       \
+    if (e_ != hipSuccess) {                                       \
+      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+      cleanup();                                                  \
+      return LC_ERR_DEVICE;                                       \
+    }                                                             \
+  } while (0)
+  CrArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.K = K;
+  A.n = n;
+  A.niter = cfg->niter;
+  A.sepmed = cfg->sepmed != 0;
+  A.have_invar = invar != nullptr;
+  A.gain = cfg->gain;
+  A.gain2 = cfg->gain * cfg->gain;
+  A.rn2 = cfg->readnoise * cfg->readnoise;
+  A.vhole = 1e-5f + A.rn2;
+  A.satg = cfg->gain * cfg->satlevel;
+  A.satg10 = A.satg / 10.0f;
+  A.sigclip = cfg->sigclip;
+  A.sigcliplow = cfg->sigfrac * cfg->sigclip;
+  A.objlim = cfg->objlim;
+  void *p = nullptr;
+  CR_TRY(alloc(tot * 4, &p));
+  A.data = (const float *)p;
+  CR_TRY(hipMemcpyAsync(p, data, tot * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (invar) {
+    CR_TRY(alloc(tot * 4, &p));
+    A.invar = (const float *)p;
+    CR_TRY(hipMemcpyAsync(p, invar, tot * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (inmask) {
+    CR_TRY(alloc(tot, &p));
+    A.inmask = (const uint8_t *)p;
+    CR_TRY(hipMemcpyAsync(p, inmask, tot, hipMemcpyHostToDevice, ctx->stream));
+  }
+  CR_TRY(alloc(tot, &p));
+  A.crmask = (uint8_t *)p;
+  if (clean) {
+    CR_TRY(alloc(tot * 4, &p));
+    A.clean = (float *)p;
+  }
+  if (iters) {
+    CR_TRY(alloc((size_t)K * 4, &p));
+    A.iters = (int *)p;
+  }
+  size_t lds_bytes = 0;
+  if (lds) {
+    lds_bytes = cr_plane_bytes(n);
+    CR_TRY(hipFuncSetAttribute((const void *)cosmics_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds_bytes));
+  } else {
+    CR_TRY(alloc((size_t)grid * cr_plane_bytes(n), &p));
+    A.scratch = (float *)p;
+  }
+  CR_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  if (lds)
+    hipLaunchKernelGGL(cosmics_kernel<true>, dim3(grid), dim3(kCrThreads), lds_bytes, ctx->stream, A);
+  else
+    hipLaunchKernelGGL(cosmics_kernel<false>, dim3(grid), dim3(kCrThreads), 0, ctx->stream, A);
+  CR_TRY(hipGetLastError());
+  CR_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  CR_TRY(hipMemcpyAsync(crmask, A.crmask, tot, hipMemcpyDeviceToHost, ctx->stream));
+  if (clean) CR_TRY(hipMemcpyAsync(clean, A.clean, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (iters) CR_TRY(hipMemcpyAsync(iters, A.iters, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
+  CR_TRY(hipStreamSynchronize(ctx->stream));
+  if (kernel_ms) CR_TRY(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+  cleanup();
+#undef CR_TRY
+  return LC_OK;
+}
+
+}  // extern "C"

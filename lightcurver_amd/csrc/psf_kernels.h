@@ -16,11 +16,8 @@
 #ifndef LC_XPOLL_SLEEP
 #define LC_XPOLL_SLEEP 2
 #endif
-#ifndef LC_PSF_WAVEFLAGS
-#define LC_PSF_WAVEFLAGS 0
-#endif
 namespace lc {
-constexpr int kXFlagStride = 16;   // flag words per (frame, role): one per wave in the per-wave form, word 0 in the workgroup form
+constexpr int kXFlagStride = 16;   // flag words per (frame, role): word 0 is the flag, the rest keeps (frame, role) pairs on lines of their own
 
 #ifdef LC_STAMPS
 __device__ long long g_stamps[128];  // [0, 64): block 0, [64, 128): block 8 (role 1 of frame 0 in the two-workgroup form)
@@ -209,6 +206,20 @@ __device__ inline void tap_entry(float delta, int k, float &tap, float &dtap, in
 // Block b serves frame (b / 16) * 8 + b % 8 in role (b / 8) % 2: partners are 8 blocks apart, which the
 // dispatcher is observed to place on one XCD (speed only).  The host launches this form only when the whole grid
 // is resident at once (one workgroup per CU), so the partner a workgroup waits for is always running.
+// Hand-off protocol of iteration t, the same in both roles: store the own half into slab t & 1 (role 1: and its l1 value), every
+// wave drains its stores, workgroup barrier, ONE lane stores t + 1 into the own flag and polls the partner's flag for t + 1
+// (bounded), barrier, every thread loads the partner's half with L1-bypassing loads, step, closing barrier.
+// * Flag first.  Each role publishes before it waits, so there is no wait cycle, and neither role's publishing depends on the
+//   partner's: the period of the pair is the longer role's own chain, not the sum of one role's chain and the other's tail.
+// * Two slabs are enough.  A role rewrites slab t & 1 at iteration t + 2, behind its loads of iteration t + 1; the partner
+//   raised the flag those loads waited for only behind its own loads of iteration t, which were the last readers of that slab.
+// * Giving up stays workgroup-uniform: one polling lane, its verdict in LDS, barrier, break.  The host clears the flag words in
+//   front of every launch (psf_batch.hip); iteration and slab parity count from 0 in every launch, t0 only selects the schedule.
+// * Which XCD the partner runs on is learned in the first hand-off of a launch (the word behind the slab, always stored
+//   write-through, read by the polling lane after the flag): until then every store of the hand-off is write-through.
+// * Pixel state in registers (N <= 64): between its stores and its flag role 0 runs only the step of the stars (first wave,
+//   beside the drain); the tap tables of the next iteration, which need that step, are made behind the drain's barrier while
+//   the one lane stores and polls.  N = 128: stars' step, barrier and tables all beside the drain, as before.
 template <class C, bool SPLIT = false>
 __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
   constexpr int N = C::N, SS = C::SS, PX = C::PX, SG = C::SG, n = C::n, NT = C::NT, J = C::J;
@@ -315,8 +326,8 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     }
   }
 
-  // ---- tap tables of every star of the frame: once before the first iteration, then right behind the star update of every
-  //      iteration - in the two-workgroup form between the hand-off stores and their drain, whose latency they hide ----------
+  // ---- tap tables of every star of the frame: once before the first iteration, then behind the star update of every
+  //      iteration - in the two-workgroup form behind the drain of role 0's hand-off stores, beside its flag round trip -------
   auto compute_taps = [&](int tid) {
     for (int e = tid; e < S * 2 * NTP; e += NTHR) {
       const int s = e / (2 * NTP), ax = (e / NTP) & 1, k = e % NTP - 1;  // k = -1, NT, NT + 1: the zero padding
@@ -332,9 +343,9 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       if (k == 0) BQ[s * 2 + ax] = bq;
     }
   };
-  // AdaBelief step of a, x0, y0 of every star (threads tid < 3 S) and the tap tables of the next iteration.  Needs the
-  // complete star gradients (SGR) and this iteration's schedule (SCAL); every thread of the workgroup calls (barrier inside).
-  auto update_stars_and_taps = [&](int tid) {
+  // AdaBelief step of a, x0, y0 of every star (threads tid < 3 S); the tap tables of the next iteration follow behind a barrier.
+  // Needs the complete star gradients (SGR) and this iteration's schedule (SCAL).
+  auto step_stars = [&](int tid) {
 #pragma clang fp contract(off)
     if (tid < S * 3) {
       const float lr = SCAL[0], bc1 = SCAL[1], bc2 = SCAL[2];
@@ -348,15 +359,13 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       SV[s * 4 + q] = sn;
       SP[s * 4 + q] -= lr * (mn * bc1) / (sqrtf(sn * bc2) + eps);
     }
+  };
+  auto update_stars_and_taps = [&](int tid) {
+    step_stars(tid);
     __syncthreads();
     compute_taps(tid);
   };
   if (conv_role) compute_taps(tid0);  // (visible behind the barrier that opens the first group of stars)
-#if LC_PSF_WAVEFLAGS
-  if constexpr (SPLIT) {
-    if (tid0 == 0) ((int *)(SCAL + 5))[0] = 1;  // (per-wave hand-off: only ever cleared; read behind the iteration's barriers)
-  }
-#endif
   // (measured and left out: s_setprio 1 for the second-dispatched half of the workgroup - MI355X_MICROARCH.md, two waves per
   //  SIMD - C2 16.2 us per iteration with and without, C3 shard 86.8 / 86.9)
   for (int it = 0; it < A.n_iter; ++it) {
@@ -989,44 +998,20 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         else store_sc1_f(mine + N * N, tl1);
       }
       if (tid == 0 && it == 0) store_sc1_f(mine + N * N + 1, __int_as_float(my_xcc + 1));
-      // role 0: the stars' step and the next tap tables need nothing from the partner: done while the stores drain
-      if (role == 0 && A.mode == 1) update_stars_and_taps(tid);
-#if LC_PSF_WAVEFLAGS
-      // (-DLC_PSF_WAVEFLAGS=1; built in round 4 and measured NOT faster: C2 14.8 against 14.8 - 14.9 us per iteration (54.0 - 54.2
-      //  against 53.7 - 53.9 M cutouts/s), C3 shard 90.4 against 82.7 - sixteen polling lanes per workgroup at N = 128.  The one-lane
-      //  form below stays the default.)
-      // Per-WAVE flags: wave w of role 0 and wave w of role 1 own the same 64 PX pixels, so a wave hands over as soon as ITS
-      // stores have drained and reads as soon as its partner wave has published - no workgroup barrier in front of the flag,
-      // eight polling lanes instead of one, and a wave does not wait for the slowest wave of either workgroup.  One barrier
-      // remains behind the reads: it makes the give-up decision uniform (a wave whose partner does not show up clears OK[0];
-      // nobody leaves the loop before everybody has seen it) and publishes what the first hand-off found out about the XCDs.
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      LC_STAMP(45);
-      int *OK = (int *)(SCAL + 5);
-      int wave_ok = 1;
-      if (lane == 0) {
-        int *myflag = A.xflags + ((size_t)f * 2 + role) * kXFlagStride + wid;
-        const int *theirflag = A.xflags + ((size_t)f * 2 + (1 - role)) * kXFlagStride + wid;
-        if (same_xcd) asm volatile("global_store_dword %0, %1, off" ::"v"(myflag), "v"(it + 1) : "memory");
-        else __hip_atomic_store(myflag, it + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int spins = 0;
-        while (__hip_atomic_load(theirflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < it + 1) {
-          __builtin_amdgcn_s_sleep(LC_XPOLL_SLEEP);
-          ++spins;
-          // exit condition every wave reaches: a partner that never shows up is reported, not waited for
-          if (spins > (1 << 21) ||
-              ((spins & 255) == 0 && __hip_atomic_load(A.xabort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.launch_seq)) {
-            __hip_atomic_store(A.xabort, A.launch_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            wave_ok = 0;
-            OK[0] = 0;
-            break;
-          }
-        }
-        if (tid == 0 && it == 0 && wave_ok)
-          OK[1] = (A.xcd_fast && __float_as_int(load_sc1_f(theirs + N * N + 1)) == my_xcc + 1) ? 1 : 0;
+      // role 0: the stars' step needs nothing from the partner: done (by the first wave) while the stores drain.  The next tap
+      // tables, which need that step, wait until the flag is up (below): in front of it they were ~1.5 k cycles by which role 0,
+      // the longer role, published late.
+      // (pixel state in registers only: at N = 128, where the update's traffic is two thirds of the tail, the C3 shard measured
+      //  82.4 / 82.4 and 82.9, 83.3 / 82.6, 82.6 us per iteration with the late tables against without: the old order stays there)
+      constexpr bool TAPS_LATE = STATE_REGS;
+      if (role == 0 && A.mode == 1) {
+        if (TAPS_LATE) step_stars(tid);
+        else update_stars_and_taps(tid);
       }
-      wave_ok = __builtin_amdgcn_readfirstlane(wave_ok);
-#else
+      // (built in round 4, measured NOT faster and taken out again: per-WAVE flags - wave w of either role owns the same 64 PX
+      //  pixels, hands over as soon as ITS stores have drained and reads as soon as its partner wave has published, no workgroup
+      //  barrier in front of the flag: C2 14.8 against 14.8 - 14.9 us per iteration, C3 shard 90.4 against 82.7 with sixteen
+      //  polling lanes per workgroup at N = 128.  DESIGN.md section 5, round 4.)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       LC_STAMP(45);
@@ -1056,18 +1041,23 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
       }
-#endif
-#if !LC_PSF_WAVEFLAGS
+      // role 0's tap tables of the next iteration, behind the barrier that follows the stars' step and beside the one lane's flag
+      // round trip: the table entries go to the upper half of the workgroup first, whose waves do not wait for that lane
+      if (TAPS_LATE && role == 0 && A.mode == 1) compute_taps((tid + NTHR / 2) % NTHR);
       __syncthreads();
       LC_STAMP(46);
       if (*OK == 0) break;
       if (it == 0) same_xcd = OK[1];
-#endif
       // (measured and left out: a first look at the partner's flag requested while the own stores drain, so that the role
       //  that arrives second skips its first poll - 15.2 against 15.0 us per iteration on one box, C3 shard 83.8 / 82.6)
-      // (measured and left out: role 0, the longer of the two, asking for the partner's half BEFORE publishing its own - the
-      //  partner has published long before - with loads the compiler tracks (agent-scope relaxed atomics, one dword each):
-      //  17.0 against 14.8 us per iteration; the 16-byte form would need registers that are in flight across compiled code)
+      // (measured and left out, twice: role 0, the longer of the two, asking for the partner's half BEFORE publishing its own.
+      //  First with loads the compiler tracks (agent-scope relaxed atomics, one dword each): 17.0 against 14.8 us per iteration.
+      //  Then with the 16-byte asm loads in front of the stores, the flag raised behind the step and the closing barrier, two
+      //  barriers fewer in role 0: bit-identical, 15.62 - 15.66 against 14.76 - 14.77, C3 shard 86.2 against 82.7.  The order
+      //  cannot win: role 1 needs gB_t to form z_(t+1), so the time from role 0's flag to z_(t+1) being visible is role 1's
+      //  whole chain (flag latency, loads, step, starlet, reduction, stores, drain, flag: ~33.9 k cycles by the stamps), and a
+      //  role 0 that raises its flag d cycles AFTER it has consumed z cannot have a period under that chain + d, where the
+      //  order here, flag first, gives chain - d.  DESIGN.md section 5, "PSF hand-off: budget and order".)
       float other[PX];
       float tl1_other = 0.f;  // (every thread reads the partner's scalar along with its pixels: one line, no second round trip)
       if constexpr (PX == 8) {
@@ -1088,12 +1078,6 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         if (role) gB[p] = other[p]; else z[p] = other[p];
       }
       if (tid == 0 && role == 0) tl1 = (PX == 8) ? tl1_other : load_sc1_f(theirs + N * N);
-#if LC_PSF_WAVEFLAGS
-      __syncthreads();
-      LC_STAMP(46);
-      if (*OK == 0) break;
-      if (it == 0) same_xcd = OK[1];
-#endif
       LC_STAMP(47);
     }
     if (tid == 0 && conv_role) {

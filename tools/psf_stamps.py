@@ -23,7 +23,7 @@ _lib.lib().lc_debug_get_stamps.argtypes = [C.POINTER(C.c_longlong)]
 assert _lib.lib().lc_debug_get_stamps(out) == 0
 allst = np.array(out[:], dtype=np.int64)
 names = {0: 'start', 1: 'P1 + taps (to first barrier)', 40: 'conv: wave tasks + P5', 42: 'starlet', 44: 'l1 reduce',
-         45: 'publish (stores, drain, barrier)', 46: 'flag + wait for partner', 47: 'read partner slab', 43: 'loss + update'}
+         45: 'publish (stores, drain, barrier)', 46: 'flag, poll (role 0: + tap tables)', 47: 'read partner slab', 43: 'loss + update'}
 order = [0, 1, 40, 42, 44, 45, 46, 47, 43]
 for blk, label in ((0, 'block 0 (role 0 / single form)'), (64, 'block 8 (role 1)')):
     s = allst[blk:blk + 64]

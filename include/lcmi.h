@@ -141,7 +141,8 @@ int lc_psf_batch_get_grid(lc_psf_batch *b, float *grid);
  * maps left by lc_psf_batch_propagate_noise / an earlier call with W != NULL. */
 int lc_psf_batch_set_regularization(lc_psf_batch *b, const float *W, float lam_scales, float lam_hf);
 /* noise propagation of the chi2 gradient into the starlet domain of B (replaces the
- * propagate_noise call inside build_psf), using the current a, x0, y0.  Writes device W. */
+ * propagate_noise call inside build_psf), using the current a, x0, y0.  Writes device W.  A star further than N/4
+ * high-resolution pixels from the stamp centre enters pinned there, as in the fit itself (device and host path). */
 int lc_psf_batch_propagate_noise(lc_psf_batch *b);
 int lc_psf_batch_get_weights(lc_psf_batch *b, float *W);
 /* One evaluation at the current parameters.  Any output may be NULL.

@@ -691,7 +691,9 @@ int lc_psf_batch_propagate_noise(lc_psf_batch *b) {
         NoiseAccumulator acc(N, ss);
         for (int s = 0; s < S; ++s) {
           const float *sp = &st[((size_t)f * S + s) * 4];
-          const double a = sp[0], dx = ss * (double)sp[1] + c_off, dy = ss * (double)sp[2] + c_off;
+          const double pin = (double)(N / 4);  // as the fit kernel and the device path pin the star's Gaussian
+          const double a = sp[0], dx = std::fmin(std::fmax(ss * (double)sp[1], -pin), pin) + c_off,
+                       dy = std::fmin(std::fmax(ss * (double)sp[2], -pin), pin) + c_off;  // (fmin / fmax: a NaN is pinned too)
           const int ox = (int)std::nearbyint(dx), oy = (int)std::nearbyint(dy);
           std::fill(r.begin(), r.end(), 0.0);
           if (a != 0.0)

@@ -30,7 +30,9 @@ __global__ void psf_noise_tables_kernel(int S, int N, int ss, int J, const float
   if (x < N) {
     for (int ax = 0; ax < 2; ++ax) {
       // ax 0: rows (y, star parameter 2), ax 1: columns (x, star parameter 1)
-      const double delta = ss * (double)sp[ax == 0 ? 2 : 1] + c_off;
+      // pinned at +-N/4 high-res pixels like the Gaussian of the fit kernel (psf_kernels.h compute_taps): the maps are
+      // the noise of the gradient that kernel computes
+      const double delta = fmin(fmax(ss * (double)sp[ax == 0 ? 2 : 1], -(double)(N / 4)), (double)(N / 4)) + c_off;
       const int o = (int)nearbyint(delta);
       double v = 0.0;
       for (int du = 0; du < ss; ++du) {

@@ -7,12 +7,18 @@ import pytest
 from oracle import model as om, optim as oo, psf_cpu
 from lightcurver_amd.synthetic import make_psf_dataset
 from tests import helpers as H
+from tests import _psf_geometry as G
 
 
-def _problem(n, ss, S, F, seed, jitter=0.2, double=False):
-    ds = make_psf_dataset(F=F, S=S, n=n, ss=ss, seed=seed)
-    rng = np.random.default_rng(seed + 1)
-    plist = [H.psf_initial_params(ds, f, ss, rng, jitter) for f in range(F)]
+def _problem(n, ss, S, F, seed, jitter=0.2, double=False, limit=False):
+    """limit: stars at the offset set of tests/_psf_geometry.py on stamps drawn from the oracle's forward model, instead of
+    the synthetic data set with its +-0.5 pixel offsets."""
+    if not limit:
+        ds = make_psf_dataset(F=F, S=S, n=n, ss=ss, seed=seed)
+        rng = np.random.default_rng(seed + 1)
+        plist = [H.psf_initial_params(ds, f, ss, rng, jitter) for f in range(F)]
+    else:
+        ds, plist, _ = G.case(n, ss, S, F, seed)
     N = n * ss
     J = om.n_scales(N)
     Tm = np.stack([om.moffat(N, ss, p['fwhm_x'], p['fwhm_y'], p['phi'], p['beta']).numpy() for p in plist])
@@ -30,22 +36,54 @@ def _problem(n, ss, S, F, seed, jitter=0.2, double=False):
     return ds, plist, Ws, st
 
 
-@pytest.mark.parametrize('n,ss,S', [(16, 1, 3), (16, 2, 4), (32, 2, 8)])
-def test_c_port_evaluation_matches_the_float64_oracle(n, ss, S):
-    F = 2
-    ds, plist, Ws, st = _problem(n, ss, S, F, 50 + n + ss)
+LIMIT_CASES = [(16, 1, 8), (16, 2, 8), (24, 2, 8), (32, 2, 8), (64, 2, 8), (32, 2, 16)]   # as tests/test_psf_geometry_gpu.py
+
+
+@pytest.mark.parametrize('n,ss,S,offsets', [(16, 1, 3, 'jitter'), (16, 2, 4, 'jitter'), (32, 2, 8, 'jitter')] +
+                         [c + ('limit',) for c in LIMIT_CASES])
+def test_c_port_evaluation_matches_the_float64_oracle(n, ss, S, offsets):
+    """'jitter': stars within 0.2 pixels of the stamp centre.  'limit': the offset set of the geometry tests (corners and
+    edges of the +-n/4 square, both sides of a rounding tie of delta, a negative-only frame), where the windows of the
+    separable passes leave the stamp - on the very inputs of test_psf_geometry_gpu.py's single-evaluation test.  The C
+    port bounds-checks every window sample and carries no aprons, so it shares none of the HIP kernels' window arithmetic:
+    that test uses it as the fp32 yardstick.  Beside the global max-norm, dL/dB is judged on its outer 8 high-resolution
+    pixels relative to the largest element there and the model per star relative to the star's own peak.  On the 'limit'
+    inputs the star gradients are judged element by element too: within 5e-5 everywhere but in dL/da of frame 1 at
+    n = 64 (a faint star, 4096 pixels, the noise outweighs the flux deficit), where fp32 reaches 1.64e-4 - the figure the
+    one wider bound of the GPU test (6.4e-4) is four times of; it is held between 5e-5 (the
+    exception is needed) and 2e-4 (the GPU bound keeps a factor of three or more over it)."""
+    if offsets == 'limit':
+        F = 3
+        ds, plist, Ws, st = _problem(n, ss, S, F, G.eval_seed(n, ss, S), limit=True)
+    else:
+        F = 2
+        ds, plist, Ws, st = _problem(n, ss, S, F, 50 + n + ss)
     N = n * ss
     out = st.evaluate(1.3, 0.7, model=True)
     for f in range(F):
         data, sig2, mask = H.psf_oracle_inputs(ds, f, ss)
         fn = lambda q: om.psf_loss(q, data, sig2, mask, ss, W=Ws[f], lam_scales=1.3, lam_hf=0.7)
         L, g = oo.value_and_grad(fn, plist[f], ['a', 'x0', 'y0', 'B'])
-        assert abs(out['loss'][f] - L) / abs(L) < 2e-5
-        assert H.rel_err(out['model'][f], om.psf_model(plist[f], ss, n).numpy()) < 2e-5
-        assert H.rel_err(out['grad_grid'][f], g['B'].numpy().reshape(N, N)) < 5e-5
+        model = om.psf_model(plist[f], ss, n).numpy()
+        gB = g['B'].numpy().reshape(N, N)
         gs = np.stack([g['a'].numpy(), g['x0'].numpy(), g['y0'].numpy()], axis=-1)
+        fine = dict(ring=G.ring_err(out['grad_grid'][f], gB), model=G.per_star_model_err(out['model'][f], model).max(),
+                    stars=[G.per_element_err(out['grad_stars'][f][:, q], gs[:, q]).max() for q in range(3)])
+        print(f'c port n={n} ss={ss} {offsets} frame {f}: loss {abs(out["loss"][f] - L) / abs(L):.2e} '
+              f'model {H.rel_err(out["model"][f], model):.2e} grid {H.rel_err(out["grad_grid"][f], gB):.2e} finer {fine}')
+        assert abs(out['loss'][f] - L) / abs(L) < 2e-5
+        assert H.rel_err(out['model'][f], model) < 2e-5
+        assert H.rel_err(out['grad_grid'][f], gB) < 5e-5
         for q in range(3):
             assert H.rel_err(out['grad_stars'][f][:, q], gs[:, q]) < 5e-5, q
+        assert fine['ring'] < 5e-5
+        assert fine['model'] < 2e-5
+        if offsets == 'limit':
+            for q in range(3):
+                if (n, f, q) == (64, 1, 0):
+                    assert 5e-5 < fine['stars'][q] < 2e-4, fine['stars']
+                else:
+                    assert fine['stars'][q] < 5e-5, (q, fine['stars'])
 
 
 def test_c_port_trajectory_matches_the_float64_oracle():
@@ -106,3 +144,42 @@ def test_frame_and_star_parallel_forms_of_the_c_port_give_the_same_bits():
         out.append((hist.copy(), st.B.copy(), st.stars.copy()))
     for h, B, stars in out[1:]:
         assert np.array_equal(h, out[0][0]) and np.array_equal(B, out[0][1]) and np.array_equal(stars, out[0][2])
+
+
+def test_a_run_started_at_the_offset_limit_leaves_it():
+    """Why the trajectory test of tests/test_psf_geometry_gpu.py starts its limit stars 0.01 pixels inside +-n/4: from the
+    limit itself a 25-iteration run carries some star past it, where the HIP kernel pins the star's Gaussian (DESIGN.md
+    section 3) and the oracle does not.  The oracle with the same pin differs from the free oracle by several 1e-3 in
+    the loss history from that start - far above the 1e-4 the trajectory is held to - and not at all from the start
+    inside, while no star comes within 4e-3 pixels of the limit there."""
+    n, ss, T = 16, 2, 25
+    lim = n / 4.0
+    free_model = om.psf_model
+
+    def pinned_model(p, ss_, n_):
+        return free_model(dict(p, x0=p['x0'].clamp(-lim, lim), y0=p['y0'].clamp(-lim, lim)), ss_, n_)
+
+    try:
+        for inside in (False, True):
+            xy = G.offsets_for(n, ss, 8, 1)
+            if inside:
+                xy = np.clip(xy, -(lim - 0.01), lim - 0.01)
+            ds = G.draw_dataset(n, ss, G.displaced(xy, 517), 516)
+            p0 = G.params_at(ds, xy, 518)[0]
+            data, sig2, mask = H.psf_oracle_inputs(ds, 0, ss)
+            W = om.propagate_noise_psf(p0, sig2, mask, ss)
+            hist = []
+            for mdl in (free_model, pinned_model):
+                om.psf_model = mdl
+                fn = lambda q: om.psf_loss(q, data, sig2, mask, ss, W=W, lam_scales=1.0, lam_hf=1.0)
+                pf, lh, l0 = oo.adabelief(fn, p0, ['B', 'a', 'x0', 'y0'], 1e-4, T, schedule=True)
+                hist.append(np.array([l0] + lh))
+            diff = np.abs(hist[0] - hist[1]).max() / np.abs(hist[0]).max()
+            reach = max(float(pf['x0'].abs().max()), float(pf['y0'].abs().max()))
+            print(f'start {"inside" if inside else "at the limit"}: pinned vs free loss history {diff:.2e}, reach {reach:.5f}')
+            if inside:
+                assert diff == 0.0 and reach < lim - 4e-3
+            else:
+                assert diff > 1e-3 and reach > lim
+    finally:
+        om.psf_model = free_model

@@ -13,7 +13,6 @@
 #include "joint_reduce_peer.h"
 #include "joint_reg_mfma.h"
 #include "joint_reg_fused.h"
-#include "joint_reg_rows.h"
 #include "joint_ps.h"
 #include "joint_noise.h"
 #include "joint_lbfgs.h"
@@ -24,6 +23,7 @@
 using namespace lc;
 
 constexpr int kMaxParts = 16;  // workgroups per epoch of the phased launches
+constexpr int kRegChainCUs = 64;  // CUs the cluster form of the epoch kernel leaves to the regulariser chain beside it (cluster_parts)
 constexpr int kRegsStride = 4 + 3 * kMaxSources + 4;  // floats of lc_joint::regs (per star of a batch with backgrounds)
 typedef void (*epoch_fn)(JointArgs);
 typedef void (*update_fn)(JointUpdArgs);
@@ -54,18 +54,10 @@ struct JointVariant {
   epoch_fn ek_tmpl = nullptr, ek_grp_tmpl = nullptr;
 };
 
-typedef void (*mreg_fn)(MregArgs);
-typedef void (*mreg_mm_fn)(MmBatch);
-typedef void (*mreg_chain_fn)(MregChainArgs);
 struct MregKernels {
   int N;
-  mreg_fn fwd, adj;
-  int lds_fwd, lds_adj, nthr;
-  mreg_mm_fn mm;  // batched tiled products of the second form of the chain (joint_reg_mfma.h)
-  mreg_chain_fn chain;  // the whole second form as one launch (null: not built for this N)
-  void (*rows)(MregRowsArgs) = nullptr;  // third form: row blocks, two stages (joint_reg_rows.h; null: not built for this N)
-  int rows_lds = 0;
-  void (*mmx[4])(MmxArgs) = {nullptr, nullptr, nullptr, nullptr};  // fourth form (default): f1', a1', a2' and the plain product of joint_reg_fused.h
+  void (*mm)(MmBatch);      // batched tiled products of the eight-launch chain (joint_reg_mfma.h)
+  void (*mmx[4])(MmxArgs);  // four-launch chain (default): f1', a1', a2' and the plain product of joint_reg_fused.h
 };
 
 struct lc_joint {
@@ -99,13 +91,9 @@ struct lc_joint {
   float *gm_pts = nullptr;  // [8] mean fluxes + [blocks][8][3] partial inner products of the point-source term
   // matrix-core form of the regulariser (joint_reg_mfma.h), N >= 128
   const struct MregKernels *mreg = nullptr;
-  float *mr_A = nullptr, *mr_AT = nullptr, *mr_C = nullptr, *mr_Z = nullptr, *mr_l1 = nullptr, *mr_pos = nullptr,
-        *mr_part = nullptr, *mr_pbar = nullptr;
-  float *mr_l1b = nullptr, *mr_posb = nullptr, *mr_S = nullptr, *mr_T = nullptr;  // second form of the chain: per-block values, S planes, product scratch
-  float *rr_Zp = nullptr;  // third form (row blocks): partial sub-gradient planes [N / 16 * kRrMaxParts][N^2]
+  float *mr_A = nullptr, *mr_AT = nullptr, *mr_C = nullptr, *mr_Z = nullptr, *mr_part = nullptr, *mr_pbar = nullptr;
+  float *mr_l1b = nullptr, *mr_posb = nullptr, *mr_S = nullptr, *mr_T = nullptr;  // per-block values, S planes, product scratch
   hipStream_t streamB = nullptr;      // the h regulariser runs here, concurrently with the epoch kernel
-  hipStream_t streamC = nullptr;      // ... and the point-source starlet term here, beside the regulariser chain (created on first use)
-  hipEvent_t evPts = nullptr;
   hipEvent_t evReg = nullptr, evUpd = nullptr;
   const void *ps_attr_fn = nullptr;   // point-source kernel whose dynamic-LDS attribute has been set
   std::vector<hipStream_t> gstreams;  // batched star photometry: the parts of the batch beyond the first run on these
@@ -163,9 +151,6 @@ struct lc_joint {
   // cluster launches of the epoch kernel (few epochs per GPU): flag words [E][kClStride], then the abort word
   unsigned int *cl_ctr = nullptr;
   unsigned int cl_base = 0;
-  unsigned int *chain_flags = nullptr;  // one-launch regulariser chain: [kChainBlocks] sync words, then the abort word
-  unsigned int chain_base = 0;
-  bool chain_off = false, chain_used = false;
   bool cluster_off = false, in_sharded_loop = false;
   // sharded loop over the library's own peer group: the reduction over the epochs publishes straight into the exchange region
   // (joint_reduce_peer_kernel: one launch for reduction + all-reduce); peer_fused_done: this iteration's launch did both
@@ -387,7 +372,7 @@ void find_ps_kernel(int N, int ss, ps_fn *fn, int *lds, bool persist = false, bo
 // us with one workgroup per epoch.  With the eight-launch regulariser chain (~60 us on the second stream) that gained nothing:
 // the chain was the iteration (66.8 against 65.0 us at 25 epochs).  With the four-launch chain (joint_reg_fused.h, ~32 us) it
 // does: 8 / 16 / 25 / 32 epochs 55.3 / 55.9 / 56.2 / 56.7 us per iteration against 64.8 / 65.1 / 65.0 / 65.3.
-// DEFAULT ("auto", also when LCMI_CLUSTER is unset) since then: six workgroups per epoch whenever they leave kChainBlocks CUs
+// DEFAULT ("auto", also when LCMI_CLUSTER is unset) since then: six workgroups per epoch whenever they leave kRegChainCUs CUs
 // to the chain (6 E + 64 <= CUs: up to 32 epochs - a rank's share of a sharded C4).  Not beyond: clusters that fill the
 // machine starve the chain (42 epochs x 6: 87.5 us, 50 x 5: 101.9, 85 x 3: 122.5), and fewer workgroups per epoch gain
 // little or lose (36 x 5: 64.1, 40 x 4: 64.0, 56 x 3: 72.8, 80 x 2: 85.9 against 65 - 67 us; again after the event behind the
@@ -399,7 +384,7 @@ int cluster_parts(const lc_joint *j) {
   const char *cl = std::getenv("LCMI_CLUSTER");
   const int per_wg = v->cl_thr / v->cl_lpf, full = (j->L / 2 + per_wg - 1) / per_wg;
   if (!cl || std::strcmp(cl, "auto") == 0) {
-    if (full > kMaxParts || full < 2 || j->E * full + kChainBlocks > j->ctx->n_cu) return 0;
+    if (full > kMaxParts || full < 2 || j->E * full + kRegChainCUs > j->ctx->n_cu) return 0;
     // (the chain must be the short one for the form to pay: the background regulariser on the matrix cores)
     return (j->mreg || !reg_h_on(j)) ? full : 0;
   }
@@ -675,24 +660,10 @@ int launch_reg_gm(lc_joint *j, hipStream_t stream, bool with_pts, bool abar_from
 
 template <int N>
 MregKernels make_mreg() {
-  MregKernels k{N, mreg_forward_kernel<N>, mreg_adjoint_kernel<N>, MregCfg<N>::LDS_FWD, MregCfg<N>::LDS_ADJ, MregCfg<N>::NTHR,
-                mreg_mm_kernel<N>, nullptr};
-  k.mmx[0] = mreg_mmx_kernel<N, 0>;
-  k.mmx[1] = mreg_mmx_kernel<N, 1>;
-  k.mmx[2] = mreg_mmx_kernel<N, 2>;
-  k.mmx[3] = mreg_mmx_kernel<N, 3>;
-  return k;
-}
-template <int N>
-MregKernels make_mreg_chain() {
-  MregKernels k = make_mreg<N>();
-  k.chain = mreg_chain_kernel<N>;
-  k.rows = mreg_rows_kernel<N>;
-  k.rows_lds = RrCfg<N>::LDS_BYTES;
-  return k;
+  return {N, mreg_mm_kernel<N>, {mreg_mmx_kernel<N, 0>, mreg_mmx_kernel<N, 1>, mreg_mmx_kernel<N, 2>, mreg_mmx_kernel<N, 3>}};
 }
 const MregKernels *find_mreg(int N) {
-  static const MregKernels table[] = {make_mreg_chain<128>(), make_mreg<256>()};
+  static const MregKernels table[] = {make_mreg<128>(), make_mreg<256>()};
   if (std::getenv("LCMI_REG_CASCADE")) return nullptr;  // the a-trous cascade kernels instead (cross-check)
   for (const auto &k : table)
     if (k.N == N) return &k;
@@ -726,288 +697,159 @@ void build_cumulative_operators(int N, int J, std::vector<float> &A, std::vector
   }
 }
 
-// starlet l1 + positivity of h (+ the point-source starlet term, mean fluxes from the parameters) on the matrix cores:
-// -> greg, regs (same contract as reg_mode 1 of joint_update_kernel)
-int launch_reg_mfma(lc_joint *j, hipStream_t stream, bool with_pts) {
+// The four batches of products of the regulariser chain: the scales s = 1 .. J of h (none with both l1 weights zero) and, where
+// the chain evaluates the point-source term as a product of its own (pts_batch), the mean point-source channel at scale 1
+struct RegBatches {
+  MmBatch f1, f2, a1, a2;
+  int nb;
+};
+RegBatches reg_batches(const lc_joint *j, bool l1_on, bool pts_batch) {
+  const size_t NNs = (size_t)j->N * j->N;
+  const int J = j->J;
+  // A_s and its transpose are banded with half-width 2 (2^s - 1): as the second operand the band follows the tile's
+  // columns, as the first its rows (LCMI_REG_DENSE=1: all K slices, the cross-check)
+  const int on = std::getenv("LCMI_REG_DENSE") ? 0 : 1;
+  RegBatches R;
+  std::memset(&R, 0, sizeof(R));
+  MmBatch &f1 = R.f1, &f2 = R.f2, &a1 = R.a1, &a2 = R.a2;
+  int nbch = 0;
+  auto add = [&](int s, const float *in, int slot) {
+    const float *As = j->mr_A + (size_t)s * NNs, *ATs = j->mr_AT + (size_t)s * NNs;
+    float *T = j->mr_T + (size_t)nbch * NNs;
+    f1.A[nbch] = in;                            f1.B[nbch] = ATs; f1.C[nbch] = T;                              // T = X AT_s
+    f2.A[nbch] = As;                            f2.B[nbch] = T;   f2.C[nbch] = j->mr_C + (size_t)slot * NNs;   // c_s = A_s T
+    a1.A[nbch] = j->mr_S + (size_t)slot * NNs;  a1.B[nbch] = As;  a1.C[nbch] = T;                              // T' = S_s A_s
+    a2.A[nbch] = ATs;                           a2.B[nbch] = T;   a2.C[nbch] = j->mr_Z + (size_t)slot * NNs;   // Z_s = AT_s T'
+    f1.band[nbch] = a1.band[nbch] = on * 1;
+    f2.band[nbch] = a2.band[nbch] = on * 2;
+    f1.hw[nbch] = f2.hw[nbch] = a1.hw[nbch] = a2.hw[nbch] = 2 * ((1 << s) - 1);
+    ++nbch;
+  };
+  if (l1_on)
+    for (int s = 1; s <= J; ++s) add(s, j->par[LC_P_H], s);
+  if (pts_batch) add(1, j->mr_pbar, J + 1);
+  R.nb = f1.nb = f2.nb = a1.nb = a2.nb = nbch;
+  return R;
+}
+
+// Four-launch chain (default, joint_reg_fused.h): the element-wise launches folded into the products and the point-source term
+// evaluated from separable tables instead of a ninth product - f1 (+ the point-source blocks), f2, a1' (S planes in the
+// operand fetch, values per tile), a2' (completion counter); the fused reduction + update adds the planes, any other consumer
+// gets greg / regs from one more launch.
+int launch_reg_fused(lc_joint *j, hipStream_t stream, bool with_pts, const RegBatches &B) {
   const MregKernels *k = j->mreg;
   const int N = j->N, NN = N * N, J = j->J, nb = (NN + kGmThreads - 1) / kGmThreads;
-  const bool l1_on = (j->cfg.lam_scales != 0.f || j->cfg.lam_hf != 0.f);
-  MregArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.J = J;
-  A.has_pts = with_pts ? 1 : 0;
-  A.s0 = l1_on ? 0 : J;
-  A.A = j->mr_A;
-  A.AT = j->mr_AT;
-  A.X = j->par[LC_P_H];
-  A.P = j->mr_pbar;
-  A.C = j->mr_C;
-  A.W = j->have_W ? j->W : nullptr;
-  A.norms = j->norms;
-  A.lam_sc = j->cfg.lam_scales;
-  A.lam_hf = j->cfg.lam_hf;
-  A.lam_pts = j->cfg.lam_pts_source;
-  A.Z = j->mr_Z;
-  A.l1p = j->mr_l1;
-  if (const char *dly = std::getenv("LCMI_REG_DELAY_US"))  // test hook: a chain that finishes after the epoch kernel
-    hipLaunchKernelGGL(mreg_delay_kernel, dim3(1), dim3(64), 0, stream, (long long)(std::atof(dly) * 100.0));  // wall_clock64: 100 MHz
-  auto launch_pbar = [&]() {
-    if (with_pts)
-      hipLaunchKernelGGL(mreg_pbar_kernel, dim3(nb), dim3(kGmThreads), 0, stream, N, j->ss, j->E, j->M, j->par[LC_P_A],
-                         j->par[LC_P_CX], j->par[LC_P_CY], j->mr_pbar);
-  };
-  // Third form (LCMI_REG_ROWS=1; N = 128): the regulariser cut by ROWS - one launch does forward products, S rows and adjoint
-  // products of a row block for a group of scales, a second adds the partial planes and the values; the point-source term as
-  // tiles in a launch of its own in front.  Three launches for the eight of the batched-product form (joint_reg_rows.h).
-  // Correct (tests/test_joint_paths_gpu.py: against the cascade and the second form) and NOT the default: measured on MI355X
-  // (profiles/r04_rows_*) its row kernel takes 45 us (35 us with a rolled product loop), the chain 57 - 63 us against ~60 us
-  // for the eight launches - a workgroup's 18 dependent 16-row products cost ~5 k cycles each, of which ~2.5 k remain with the
-  // operand loads and the matrix products switched off (LCMI_REG_ROWS_DBG=7): a few hundred instructions per product issued
-  // by two waves per SIMD, not memory and not the matrix pipe.  C4 83.9 against 71.1 us per iteration, its 25-epoch shard 76.8
-  // against 65.0.
-  // (its completion signal is a counter - every block of the last launch adds one - so only the flag-reading update of the
-  //  device loop and the event-waiting forms can follow it: both read reg_flag / wait for the stream)
-  {
-    const char *rr_env = std::getenv("LCMI_REG_ROWS");
-    if (k->rows && j->rr_Zp && l1_on && J == 7 && rr_env && std::atoi(rr_env) != 0 && !std::getenv("LCMI_REG_MFMA_V1")) {
-      // scale groups per row block, of about equal cost (the products of a scale cover its band: the first scales are cheap);
-      // at most kRrBatch scales each: three groups {1 .. 4}, {5, 6}, {7} (default) or two {1 .. 4}, {5 .. 7}
-      int nparts = 3;
-      if (const char *pe = std::getenv("LCMI_REG_ROWS_PARTS")) nparts = std::min(std::max(2, std::atoi(pe)), kRrMaxParts);
-      MregRowsArgs Q;
-      std::memset(&Q, 0, sizeof(Q));
-      Q.J = J;
-      Q.nparts = nparts;
-      const int lo3[3] = {1, 5, 7}, hi3[3] = {4, 6, 7}, lo2[2] = {1, 5}, hi2[2] = {4, 7};
-      for (int p = 0; p < nparts; ++p) {
-        Q.s_lo[p] = (nparts == 3) ? lo3[p] : lo2[p];
-        Q.s_hi[p] = (nparts == 3) ? hi3[p] : hi2[p];
-      }
-      Q.A = j->mr_A;
-      Q.AT = j->mr_AT;
-      Q.X = j->par[LC_P_H];
-      Q.W = j->have_W ? j->W : nullptr;
-      Q.norms = j->norms;
-      Q.lam_sc = j->cfg.lam_scales;
-      Q.lam_hf = j->cfg.lam_hf;
-      Q.lam_pos = j->cfg.lam_positivity;
-      Q.Zp = j->rr_Zp;
-      Q.S0 = j->mr_S;
-      Q.vals = j->mr_l1b;
-      if (const char *dg = std::getenv("LCMI_REG_ROWS_DBG")) Q.dbg = std::atoi(dg);
-      const int tiles = (N / kPtT) * (N / kPtT), nwg = (N / kRrRows) * nparts;
-      if (with_pts)
-        hipLaunchKernelGGL(gm_pts_direct_kernel, dim3(tiles), dim3(kGmThreads), 0, stream, N, j->ss, j->M, j->a_ref, (const float *)nullptr,
-                           j->par[LC_P_CX], j->par[LC_P_CY], Q.W, j->norms, j->cfg.lam_pts_source, j->mr_part, j->mr_posb,
-                           (const float *)j->par[LC_P_A], j->E);
-      LC_HIP(j->ctx, hipFuncSetAttribute((const void *)k->rows, hipFuncAttributeMaxDynamicSharedMemorySize, k->rows_lds));
-      hipLaunchKernelGGL(k->rows, dim3(nwg), dim3(kRrThreads), k->rows_lds, stream, Q);
-      const int nfin = NN / kGmThreads + 1;
-      j->reg_seq += (unsigned int)nfin;
-      hipLaunchKernelGGL(mreg_rows_finish_kernel, dim3(nfin), dim3(kGmThreads), 0, stream, NN, nwg, j->rr_Zp, j->mr_S, j->greg,
-                         j->mr_l1b, with_pts ? 1 : 0, tiles, j->M, j->mr_part, j->mr_posb, j->regs, j->reg_flag);
-      LC_HIP(j->ctx, hipGetLastError());
-      return LC_OK;
-    }
+  MmxArgs Q;
+  std::memset(&Q, 0, sizeof(Q));
+  for (int b = 0; b < B.nb; ++b) Q.scale[b] = b + 1;
+  Q.J = J;
+  Q.ntile = (N / 64) * (N / 64);
+  Q.X = j->par[LC_P_H]; Q.C = j->mr_C; Q.W = j->have_W ? j->W : nullptr; Q.norms = j->norms;
+  Q.lam_sc = j->cfg.lam_scales; Q.lam_hf = j->cfg.lam_hf; Q.lam_pos = j->cfg.lam_positivity;
+  Q.S = j->mr_S;
+  Q.vals = j->mr_l1b;
+  const dim3 mgrid(N / 64, N / 64, B.nb), mblock(kMmThreads);
+  dim3 g1 = mgrid;
+  if (with_pts) {   // the point-source blocks ride in the first launch (they depend on nothing the chain computes)
+    PtsSepArgs &P = Q.pts;
+    P.N = N; P.ss = j->ss; P.E = j->E; P.M = j->M;
+    P.a = j->par[LC_P_A]; P.cx = j->par[LC_P_CX]; P.cy = j->par[LC_P_CY];
+    P.W0 = j->have_W ? j->W : nullptr; P.norms = j->norms; P.lam_pts = j->cfg.lam_pts_source;
+    P.part = j->mr_part;
+    g1.z += (kPtsBlocks + Q.ntile - 1) / Q.ntile;
   }
-  if (!std::getenv("LCMI_REG_MFMA_V1")) {
-    // second form: batched tiled products over the scales, telescoped adjoint
-    const size_t NNs = (size_t)NN;
-    auto At = [&](int s) { return j->mr_AT + (size_t)s * NNs; };
-    auto Ap = [&](int s) { return j->mr_A + (size_t)s * NNs; };
-    // LCMI_PTS_SIDE=1: the point-source starlet term (scale 0 only) beside the chain instead of inside it - as tiles in ONE
-    // launch (gm_pts_direct_kernel, joint_gm.h; mean fluxes from the fluxes themselves) on a third stream, joined in front of
-    // the sums; inside the chain it is a launch of its own for Pbar plus one more product in each of the four batches.  Equal
-    // to the batched form to fp32 rounding (tests/test_joint_paths_gpu.py).  Built to take the Pbar launch off a chain that
-    // ends just after the epoch kernel; measured SLOWER and not the default: C4 81.0 against 70.9 us per iteration, its
-    // 25-epoch shard 66.4 / 64.4, the C5 shard 235.5 / 230.7 - the third stream's fork and join (two more cross-stream event
-    // waits per iteration, a third hardware queue) cost more than the launch they remove.  (In a process that has created many
-    // streams the runtime may map two of the three onto one hardware queue; with the update's in-kernel wait for the chain
-    // (the default) a run of this form then timed out once in the test suite: use it with LCMI_EVENT_SYNC=1.)
-    const char *ps_env = std::getenv("LCMI_PTS_SIDE");
-    const bool pts_side = with_pts && stream == j->streamB && N % kPtT == 0 && ps_env && std::atoi(ps_env) != 0 && !std::getenv("LCMI_REG_CHAIN");
-    if (pts_side) {
-      if (!j->streamC) {
-        LC_HIP(j->ctx, hipStreamCreate(&j->streamC));
-        LC_HIP(j->ctx, hipEventCreateWithFlags(&j->evPts, hipEventDisableTiming));
-      }
-      LC_HIP(j->ctx, hipStreamWaitEvent(j->streamC, j->evUpd, 0));   // (what the chain's own stream waited for)
-      const int tiles = (N / kPtT) * (N / kPtT);
-      hipLaunchKernelGGL(gm_pts_direct_kernel, dim3(tiles), dim3(kGmThreads), 0, j->streamC, N, j->ss, j->M, j->a_ref, (const float *)nullptr,
-                         j->par[LC_P_CX], j->par[LC_P_CY], j->have_W ? j->W : nullptr, j->norms, j->cfg.lam_pts_source, j->mr_part,
-                         j->mr_l1b + (size_t)(J + 1) * nb, (const float *)j->par[LC_P_A], j->E);
-      LC_HIP(j->ctx, hipEventRecord(j->evPts, j->streamC));
-    }
-    // Fourth form (default; LCMI_REG_FUSED=0: the eight launches below): the element-wise launches folded into the products and
-    // the point-source term evaluated from separable tables instead of a ninth product (joint_reg_fused.h) - f1 (+ the
-    // point-source blocks), f2, a1' (S planes in the operand fetch, values per tile), a2' (completion counter); the fused
-    // reduction + update adds the planes, any other consumer gets greg / regs from one more launch.
-    const char *rc_env = std::getenv("LCMI_REG_CHAIN");
-    const char *fu_env = std::getenv("LCMI_REG_FUSED");
-    const bool fused = k->mmx[0] && l1_on && J <= kPlanesMaxJ && J <= 12 && !pts_side && !(rc_env && std::atoi(rc_env) != 0) &&
-                       !(fu_env && std::atoi(fu_env) == 0) && NN % (kPtsBlocks * kMmThreads) == 0;
-    const bool pts_batch = with_pts && !pts_side && !fused;
-    MmBatch f1, f2, a1, a2;
-    std::memset(&f1, 0, sizeof(f1));
-    f2 = a1 = a2 = f1;
-    int nbch = 0;
-    auto add = [&](int s, const float *in, float *cplane, const float *splane, float *zplane) {
-      float *T = j->mr_T + (size_t)nbch * NNs;
-      f1.A[nbch] = in;      f1.B[nbch] = At(s); f1.C[nbch] = T;        // T = X AT_s
-      f2.A[nbch] = Ap(s);   f2.B[nbch] = T;     f2.C[nbch] = cplane;   // c_s = A_s T
-      a1.A[nbch] = splane;  a1.B[nbch] = Ap(s); a1.C[nbch] = T;        // T' = S_s A_s
-      a2.A[nbch] = At(s);   a2.B[nbch] = T;     a2.C[nbch] = zplane;   // Z_s = AT_s T'
-      // A_s and its transpose are banded with half-width 2 (2^s - 1): as the second operand the band follows the tile's
-      // columns, as the first its rows (LCMI_REG_DENSE=1: all K slices, the cross-check)
-      const int hw = 2 * ((1 << s) - 1), on = std::getenv("LCMI_REG_DENSE") ? 0 : 1;
-      f1.band[nbch] = a1.band[nbch] = on * 1;
-      f2.band[nbch] = a2.band[nbch] = on * 2;
-      f1.hw[nbch] = f2.hw[nbch] = a1.hw[nbch] = a2.hw[nbch] = hw;
-      ++nbch;
-    };
-    if (l1_on)
-      for (int s = 1; s <= J; ++s) add(s, j->par[LC_P_H], j->mr_C + (size_t)s * NNs, j->mr_S + (size_t)s * NNs, j->mr_Z + (size_t)s * NNs);
-    if (pts_batch) add(1, j->mr_pbar, j->mr_C + (size_t)(J + 1) * NNs, j->mr_S + (size_t)(J + 1) * NNs, j->mr_Z + (size_t)(J + 1) * NNs);
-    f1.nb = f2.nb = a1.nb = a2.nb = nbch;
-    // The whole chain as ONE launch (mreg_chain_kernel; LCMI_REG_CHAIN=1) where its kChainBlocks workgroups are resident beside
-    // the epoch kernel's.  Same stages, same bits (tests/test_joint_cluster_gpu.py).  Built on the premise that the eight
-    // launches (5 - 7.5 us each for 1 - 2 us of work, ~60 us per iteration at N = 128) are launch overhead; measured, they
-    // are not: the one launch takes 59.4 us per iteration (profiles/r04_cluster_*) - every stage boundary is a hand-off
-    // between CUs (write-through stores, drain, flag, L1-bypassing loads from the memory side), 5 - 7 us whether a launch
-    // boundary or an in-kernel sync delivers it.  NOT the default; what shortens the chain is fewer stages, not cheaper ones.
-    if (fused) {
-      MmxArgs Q;
-      std::memset(&Q, 0, sizeof(Q));
-      for (int b = 0; b < nbch; ++b) Q.scale[b] = b + 1;
-      Q.J = J;
-      Q.ntile = (N / 64) * (N / 64);
-      Q.X = j->par[LC_P_H]; Q.C = j->mr_C; Q.W = j->have_W ? j->W : nullptr; Q.norms = j->norms;
-      Q.lam_sc = j->cfg.lam_scales; Q.lam_hf = j->cfg.lam_hf; Q.lam_pos = j->cfg.lam_positivity;
-      Q.S = j->mr_S;
-      Q.vals = j->mr_l1b;
-      const dim3 mgrid(N / 64, N / 64, nbch), mblock(kMmThreads);
-      dim3 g1 = mgrid;
-      if (with_pts) {   // the point-source blocks ride in the first launch (they depend on nothing the chain computes)
-        PtsSepArgs &P = Q.pts;
-        P.N = N; P.ss = j->ss; P.E = j->E; P.M = j->M;
-        P.a = j->par[LC_P_A]; P.cx = j->par[LC_P_CX]; P.cy = j->par[LC_P_CY];
-        P.W0 = j->have_W ? j->W : nullptr; P.norms = j->norms; P.lam_pts = j->cfg.lam_pts_source;
-        P.part = j->mr_part;
-        g1.z += (kPtsBlocks + Q.ntile - 1) / Q.ntile;
-      }
-      Q.mm = f1;
-      hipLaunchKernelGGL(k->mmx[0], g1, mblock, 0, stream, Q);
-      Q.mm = f2;
-      hipLaunchKernelGGL(k->mmx[3], mgrid, mblock, 0, stream, Q);   // (the plain product, without mreg_mm_kernel's 48 bytes of scratch per lane)
-      Q.mm = a1;
-      hipLaunchKernelGGL(k->mmx[1], mgrid, mblock, 0, stream, Q);
-      Q.mm = a2;
-      // who adds the planes up: the fused update itself when the chain is the longer path of the iteration (beside the cluster
-      // form of the epoch kernel: one stage less on the chain, ~1.3 us more in the update), otherwise a fifth launch of the
-      // chain, which then has the time (it ends ~15 us before a one-workgroup epoch kernel does)
-      const bool planes = j->planes_pred && j->reg_flag && cluster_parts(j) >= 2;
-      Q.done = planes ? j->reg_flag : nullptr;
-      hipLaunchKernelGGL(k->mmx[2], mgrid, mblock, 0, stream, Q);
-      RegPlanes &P = j->planes;
-      P.on = 1; P.J = J; P.ntile = Q.ntile; P.npts = with_pts ? kPtsBlocks : 0;
-      P.S0 = j->mr_S; P.Z = j->mr_Z; P.vals = j->mr_l1b; P.pts_part = j->mr_part;
-      if (planes) {
-        j->reg_seq += (unsigned int)(mgrid.x * mgrid.y * mgrid.z);
-        j->reg_planes = true;
-      } else {
-        // (the completion counter also serves the multi-block update of the sharded drive, which checks it in its kernel)
-        unsigned int *done = ((j->planes_pred || j->in_sharded_loop) && j->reg_flag) ? j->reg_flag : nullptr;
-        hipLaunchKernelGGL(mreg_finish3_kernel, dim3(nb + 1), dim3(kGmThreads), 0, stream, NN, nb, j->M, P, j->greg, j->regs, done);
-        if (done) j->reg_seq += (unsigned int)(nb + 1);
-        else j->reg_noflag = true;
-        j->reg_counter = done != nullptr;
-      }
-      LC_HIP(j->ctx, hipGetLastError());
-      return LC_OK;
-    }
-    const int epoch_wgs = j->E * std::max(1, cluster_parts(j));
-    if (k->chain && j->chain_flags && j->reg_flag && !j->chain_off && epoch_wgs + kChainBlocks <= j->ctx->n_cu && rc_env && std::atoi(rc_env) != 0) {
-      MregChainArgs Q;
-      std::memset(&Q, 0, sizeof(Q));
-      Q.mm[0] = f1; Q.mm[1] = f2; Q.mm[2] = a1; Q.mm[3] = a2;
-      Q.xa[0] = 0; Q.xb[0] = 0;   // T = X AT_s (h or Pbar: Pbar is a product of this launch)
-      Q.xa[1] = 0; Q.xb[1] = 1;   // c_s = A_s T
-      Q.xa[2] = 1; Q.xb[2] = 0;   // T' = S_s A_s
-      Q.xa[3] = 0; Q.xb[3] = 1;   // Z_s = AT_s T'
-      if (with_pts) Q.xa[0] = 2;  // (the last product of the batch reads Pbar: see chain_mm_tile's caller)
-      Q.G.B = A;
-      Q.G.lam_pos = j->cfg.lam_positivity;
-      Q.G.has_l1 = l1_on ? 1 : 0;
-      Q.G.S = j->mr_S;
-      Q.G.l1b = j->mr_l1b;
-      Q.G.posb = j->mr_posb;
-      Q.sslots = (l1_on ? J + 1 : 1) + (with_pts ? 1 : 0);
-      Q.with_pts = with_pts ? 1 : 0;
-      Q.N = N; Q.ss = j->ss; Q.E = j->E; Q.M = j->M; Q.J = J; Q.has_l1 = l1_on ? 1 : 0;
-      Q.a = j->par[LC_P_A]; Q.cx = j->par[LC_P_CX]; Q.cy = j->par[LC_P_CY];
-      Q.pbar = j->mr_pbar;
-      Q.S = j->mr_S; Q.Z = j->mr_Z;
-      Q.greg = j->greg; Q.pts_part = j->mr_part;
-      Q.regs = j->regs;
-      j->reg_seq += 1;
-      Q.done_flag = j->reg_flag; Q.done_seq = j->reg_seq;
-      Q.flags = j->chain_flags; Q.base = j->chain_base;
-      j->chain_base = (j->chain_base + (unsigned int)kChainSyncs) & 0x0fffffffu;
-      hipLaunchKernelGGL(k->chain, dim3(kChainBlocks), dim3(kMmThreads), 0, stream, Q);
-      LC_HIP(j->ctx, hipGetLastError());
-      j->chain_used = true;
-      return LC_OK;
-    }
-    const dim3 mgrid(N / 64, N / 64, nbch), mblock(kMmThreads);
-    if (pts_batch) launch_pbar();
-    if (nbch > 0) {
-      hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, f1);
-      hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, f2);
-    }
-    MregSArgs G;
-    std::memset(&G, 0, sizeof(G));
-    G.B = A;
-    G.lam_pos = j->cfg.lam_positivity;
-    G.has_l1 = l1_on ? 1 : 0;
-    G.S = j->mr_S;
-    G.l1b = j->mr_l1b;
-    G.posb = j->mr_posb;
-    G.B.has_pts = pts_batch ? 1 : 0;
-    const int sslots = (l1_on ? J + 1 : 1) + (pts_batch ? 1 : 0);  // slot 0 always: it carries the positivity term
-    hipLaunchKernelGGL(mreg_splanes_kernel, dim3(nb, sslots), dim3(kGmThreads), 0, stream, G, NN);
-    if (nbch > 0) {
-      hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, a1);
-      hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, a2);
-    }
-    // (the tiles of the point-source term, on the third stream, are joined here: the sums below read their partials)
-    if (pts_side) LC_HIP(j->ctx, hipStreamWaitEvent(stream, j->evPts, 0));
-    hipLaunchKernelGGL(mreg_finish2_kernel, dim3(nb), dim3(kGmThreads), 0, stream, N, J, l1_on ? 1 : 0, pts_batch ? 1 : 0, j->ss, j->M,
-                       j->mr_S, j->mr_Z, j->par[LC_P_CX], j->par[LC_P_CY], j->greg, j->mr_part);
-    j->reg_seq += 1;
-    hipLaunchKernelGGL(mreg_regs2_kernel, dim3(1), dim3(64), 0, stream, J, l1_on ? 1 : 0, with_pts ? 1 : 0, nb, j->M, j->mr_l1b,
-                       j->mr_posb, j->mr_part, j->regs, j->reg_flag, j->reg_seq);
-    LC_HIP(j->ctx, hipGetLastError());
-    return LC_OK;
+  Q.mm = B.f1;
+  hipLaunchKernelGGL(k->mmx[0], g1, mblock, 0, stream, Q);
+  Q.mm = B.f2;
+  hipLaunchKernelGGL(k->mmx[3], mgrid, mblock, 0, stream, Q);   // (the plain product, without mreg_mm_kernel's 48 bytes of scratch per lane)
+  Q.mm = B.a1;
+  hipLaunchKernelGGL(k->mmx[1], mgrid, mblock, 0, stream, Q);
+  Q.mm = B.a2;
+  // who adds the planes up: the fused update itself when the chain is the longer path of the iteration (beside the cluster
+  // form of the epoch kernel: one stage less on the chain, ~1.3 us more in the update), otherwise a fifth launch of the
+  // chain, which then has the time (it ends ~15 us before a one-workgroup epoch kernel does)
+  const bool planes = j->planes_pred && j->reg_flag && cluster_parts(j) >= 2;
+  Q.done = planes ? j->reg_flag : nullptr;
+  hipLaunchKernelGGL(k->mmx[2], mgrid, mblock, 0, stream, Q);
+  RegPlanes &P = j->planes;
+  P.on = 1; P.J = J; P.ntile = Q.ntile; P.npts = with_pts ? kPtsBlocks : 0;
+  P.S0 = j->mr_S; P.Z = j->mr_Z; P.vals = j->mr_l1b; P.pts_part = j->mr_part;
+  if (planes) {
+    j->reg_seq += (unsigned int)(mgrid.x * mgrid.y * mgrid.z);
+    j->reg_planes = true;
+  } else {
+    // (the completion counter also serves the multi-block update of the sharded drive, which checks it in its kernel)
+    unsigned int *done = ((j->planes_pred || j->in_sharded_loop) && j->reg_flag) ? j->reg_flag : nullptr;
+    hipLaunchKernelGGL(mreg_finish3_kernel, dim3(nb + 1), dim3(kGmThreads), 0, stream, NN, nb, j->M, P, j->greg, j->regs, done);
+    if (done) j->reg_seq += (unsigned int)(nb + 1);
+    else j->reg_noflag = true;
+    j->reg_counter = done != nullptr;
   }
-  launch_pbar();
-  const int slots = (l1_on ? J : 0) + (with_pts ? 1 : 0);
-  if (slots > 0) {
-    hipLaunchKernelGGL(k->fwd, dim3(N / 32, slots), dim3(k->nthr), k->lds_fwd, stream, A);
-    hipLaunchKernelGGL(k->adj, dim3(N / 32, slots), dim3(k->nthr), k->lds_adj, stream, A);
-  }
-  hipLaunchKernelGGL(mreg_finish_kernel, dim3(nb), dim3(kGmThreads), 0, stream, N, J, l1_on ? 1 : 0, with_pts ? 1 : 0, j->ss,
-                     j->M, j->mr_Z, j->par[LC_P_H], j->cfg.lam_positivity, j->par[LC_P_CX], j->par[LC_P_CY], j->greg,
-                     j->mr_pos, j->mr_part);
-  j->reg_seq += 1;
-  hipLaunchKernelGGL(mreg_regs_kernel, dim3(1), dim3(64), 0, stream, J, l1_on ? 1 : 0, with_pts ? 1 : 0, nb, j->M, j->mr_l1,
-                     j->mr_pos, j->mr_part, j->regs, j->reg_flag, j->reg_seq);
   LC_HIP(j->ctx, hipGetLastError());
   return LC_OK;
 }
 
+// Eight-launch chain (joint_reg_mfma.h): Pbar, f1, f2, the S planes and values, a1, a2, the sums, the completion flag.  What
+// runs where the four-launch form does not apply, and the form it is bit-compared with.
+int launch_reg_batched(lc_joint *j, hipStream_t stream, bool with_pts, bool l1_on, const RegBatches &B) {
+  const MregKernels *k = j->mreg;
+  const int N = j->N, NN = N * N, J = j->J, nb = (NN + kGmThreads - 1) / kGmThreads;
+  const dim3 mgrid(N / 64, N / 64, B.nb), mblock(kMmThreads);
+  if (with_pts)
+    hipLaunchKernelGGL(mreg_pbar_kernel, dim3(nb), dim3(kGmThreads), 0, stream, N, j->ss, j->E, j->M, j->par[LC_P_A],
+                       j->par[LC_P_CX], j->par[LC_P_CY], j->mr_pbar);
+  if (B.nb > 0) {
+    hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, B.f1);
+    hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, B.f2);
+  }
+  MregSArgs G;
+  std::memset(&G, 0, sizeof(G));
+  G.J = J;
+  G.has_l1 = l1_on ? 1 : 0;
+  G.X = j->par[LC_P_H];
+  G.P = j->mr_pbar;
+  G.C = j->mr_C;
+  G.W = j->have_W ? j->W : nullptr;
+  G.norms = j->norms;
+  G.lam_sc = j->cfg.lam_scales;
+  G.lam_hf = j->cfg.lam_hf;
+  G.lam_pts = j->cfg.lam_pts_source;
+  G.lam_pos = j->cfg.lam_positivity;
+  G.S = j->mr_S;
+  G.l1b = j->mr_l1b;
+  G.posb = j->mr_posb;
+  const int sslots = (l1_on ? J + 1 : 1) + (with_pts ? 1 : 0);  // slot 0 always: it carries the positivity term
+  hipLaunchKernelGGL(mreg_splanes_kernel, dim3(nb, sslots), dim3(kGmThreads), 0, stream, G, NN);
+  if (B.nb > 0) {
+    hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, B.a1);
+    hipLaunchKernelGGL(k->mm, mgrid, mblock, 0, stream, B.a2);
+  }
+  hipLaunchKernelGGL(mreg_finish2_kernel, dim3(nb), dim3(kGmThreads), 0, stream, N, J, l1_on ? 1 : 0, with_pts ? 1 : 0, j->ss, j->M,
+                     j->mr_S, j->mr_Z, j->par[LC_P_CX], j->par[LC_P_CY], j->greg, j->mr_part);
+  j->reg_seq += 1;
+  hipLaunchKernelGGL(mreg_regs2_kernel, dim3(1), dim3(64), 0, stream, J, l1_on ? 1 : 0, with_pts ? 1 : 0, nb, j->M, j->mr_l1b,
+                     j->mr_posb, j->mr_part, j->regs, j->reg_flag, j->reg_seq);
+  LC_HIP(j->ctx, hipGetLastError());
+  return LC_OK;
+}
+
+// starlet l1 + positivity of h (+ the point-source starlet term, mean fluxes from the parameters) on the matrix cores:
+// -> greg, regs (same contract as reg_mode 1 of joint_update_kernel)
+int launch_reg_mfma(lc_joint *j, hipStream_t stream, bool with_pts) {
+  const int NN = j->N * j->N, J = j->J;
+  const bool l1_on = (j->cfg.lam_scales != 0.f || j->cfg.lam_hf != 0.f);
+  if (const char *dly = std::getenv("LCMI_REG_DELAY_US"))  // test hook: a chain that finishes after the epoch kernel
+    hipLaunchKernelGGL(mreg_delay_kernel, dim3(1), dim3(64), 0, stream, (long long)(std::atof(dly) * 100.0));  // wall_clock64: 100 MHz
+  // the four-launch form wants an l1 term (the values ride in its products), room for the planes' slots and whole point-source
+  // blocks; LCMI_REG_FUSED=0: the eight launches, the test hook of the bit comparison
+  const char *fu_env = std::getenv("LCMI_REG_FUSED");
+  const bool fused = l1_on && J <= kPlanesMaxJ && J <= 12 && NN % (kPtsBlocks * kMmThreads) == 0 && !(fu_env && std::atoi(fu_env) == 0);
+  const RegBatches B = reg_batches(j, l1_on, with_pts && !fused);
+  return fused ? launch_reg_fused(j, stream, with_pts, B) : launch_reg_batched(j, stream, with_pts, l1_on, B);
+}
+
 // May the event behind an update be left out?  Inside the library's loops, on the main stream, where its only reader is the
-// next iteration's chain, which can start behind a gate kernel instead (LCMI_UPD_EVENT=1: the event, the cross-check; the
-// third stream of LCMI_PTS_SIDE waits for the event too).
+// next iteration's chain, which can start behind a gate kernel instead (LCMI_UPD_EVENT=1: the event, the cross-check).
 // One probe per object (mreg_probe_kernel): do the chain's stream and the main stream run side by side?
 static int probe_streams(lc_joint *j) {
   if (j->streams_overlap >= 0 || !j->upd_ctr) return LC_OK;
@@ -1031,7 +873,7 @@ static bool upd_gate_ok(const lc_joint *j, hipStream_t stream) {
   // (LCMI_EVENT_SYNC=1 - what counter collection sets, which runs one kernel at a time: a gate kernel alone on the machine
   //  would wait for an epoch kernel that cannot start - keeps the event as well)
   return j->upd_ctr && (j->in_device_loop || j->in_sharded_loop) && stream == j->ctx->stream && !std::getenv("LCMI_UPD_EVENT") &&
-         !std::getenv("LCMI_EVENT_SYNC") && !std::getenv("LCMI_PTS_SIDE");
+         !std::getenv("LCMI_EVENT_SYNC");
 }
 // Wait (on `stream`) for the regulariser chain of this iteration through its event.  The event is recorded HERE, behind the chain
 // on its own stream, the first time somebody needs it - the iterations whose consumer learns of the chain's completion in a
@@ -1386,7 +1228,6 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
   if ((v->gspec || cluster_ok) && !lean) TRY(dmalloc(j, &j->spec, (size_t)E * N * ((KH + 15) / 16 * 16)));  // rows padded to 128-byte lines (JointCfg::KS)
   if ((v->gspec || cluster_ok) && !lean) TRY(dmalloc(j, &j->part, (size_t)E * kMaxParts * (4 + 3 * kMaxSources)));
   if (cluster_ok) TRY(dmalloc(j, &j->cl_ctr, (size_t)(E + 1) * kClStride));
-  if (!lean) TRY(dmalloc(j, &j->chain_flags, kChainBlocks + 32));
   if (v->gspec && !lean) TRY(dmalloc(j, &j->tshift, (size_t)E * 2));
   if (G > 0) {
     std::vector<int> grp(E);
@@ -1435,17 +1276,11 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
     TRY(dmalloc(j, &j->mr_posb, nb));
     TRY(dmalloc(j, &j->mr_S, (size_t)(j->J + 2) * NN));
     TRY(dmalloc(j, &j->mr_T, (size_t)(j->J + 1) * NN));
-    TRY(dmalloc(j, &j->mr_l1, j->J + 1));
-    TRY(dmalloc(j, &j->mr_pos, nb));
     TRY(dmalloc(j, &j->mr_part, std::max<size_t>((size_t)nb * 3 * kMaxSources, (size_t)kPtsBlocks * kPtsStride)));
     TRY(dmalloc(j, &j->mr_pbar, NN));
-    if (j->mreg->rows) TRY(dmalloc(j, &j->rr_Zp, (size_t)(N / kRrRows) * kRrMaxParts * NN));
     TRY(dmalloc(j, &j->pts_ctr, 4));
     TRY(dmalloc(j, &j->upd_ctr, 4));
     TRY(dmalloc(j, &j->reg_flag, 4));  // [0] completion flag, [1] a wait ran out, [2] ticket of the finishing launch
-    LC_HIP(ctx, hipFuncSetAttribute((const void *)j->mreg->fwd, hipFuncAttributeMaxDynamicSharedMemorySize, j->mreg->lds_fwd));
-    LC_HIP(ctx, hipFuncSetAttribute((const void *)j->mreg->adj, hipFuncAttributeMaxDynamicSharedMemorySize, j->mreg->lds_adj));
-
   }
   LC_HIP(ctx, hipStreamCreate(&j->streamB));
   LC_HIP(ctx, hipEventCreateWithFlags(&j->evReg, hipEventDisableTiming));
@@ -1533,11 +1368,6 @@ void lc_joint_destroy(lc_joint *j) {
     hipStreamSynchronize(j->streamB);
     hipStreamDestroy(j->streamB);
   }
-  if (j->streamC) {
-    hipStreamSynchronize(j->streamC);
-    hipStreamDestroy(j->streamC);
-  }
-  if (j->evPts) hipEventDestroy(j->evPts);
   for (hipStream_t st : j->gstreams) {
     hipStreamSynchronize(st);
     hipStreamDestroy(st);
@@ -1996,7 +1826,6 @@ int lc_joint_step_update(lc_joint *j, const lc_adabelief_cfg *cfg) {
   return LC_OK;
 }
 
-static int chain_check(lc_joint *j);
 int lc_joint_step_grad(lc_joint *j, float *loss, float *const grads[LC_P_COUNT]) {
   if (!j) return LC_ERR_INVALID;
   LC_ENTER(j->ctx);
@@ -2017,7 +1846,7 @@ int lc_joint_step_grad(lc_joint *j, float *loss, float *const grads[LC_P_COUNT])
     for (int k = 0; k < LC_P_COUNT; ++k)
       if (grads[k] && k != LC_P_ALPHA && (rc = d2h(j, grads[k], j->gout[k], (size_t)j->psize[k] * sizeof(float)))) return rc;
   LC_HIP(j->ctx, hipStreamSynchronize(j->ctx->stream));
-  return chain_check(j);
+  return LC_OK;
 }
 
 // Cluster launches (joint_kernels.h, PHASE = 7): did a barrier wait of the launches since the last check run out?  Reads the
@@ -2037,22 +1866,6 @@ static int cluster_check(lc_joint *j, int *aborted) {
   j->cl_fallbacks += 1;
   *aborted = 1;
   return LC_OK;
-}
-
-// One-launch regulariser chains since the last check: did a sync of one give up (its workgroups were not resident together)?
-// Then its outputs were never completed: the numbers of the run are invalid; the object keeps the launch form from here on.
-static int chain_check(lc_joint *j) {
-  if (!j->chain_flags || !j->chain_used) return LC_OK;
-  j->chain_used = false;
-  unsigned int word = 0;
-  int rc = d2h(j, &word, j->chain_flags + kChainBlocks, sizeof(word));
-  if (rc || !word) return rc;
-  LC_HIP(j->ctx, hipStreamSynchronize(j->streamB));
-  LC_HIP(j->ctx, hipMemsetAsync(j->chain_flags, 0, (kChainBlocks + 32) * sizeof(unsigned int), j->ctx->stream));
-  LC_HIP(j->ctx, hipStreamSynchronize(j->ctx->stream));
-  j->chain_base = 0;
-  j->chain_off = true;
-  LC_FAIL(j->ctx, LC_ERR_DEVICE, "joint fit: the one-launch regulariser chain gave up (its workgroups were not resident together); this run's numbers are invalid - the object has switched to the launch form, run again (LCMI_REG_CHAIN=0 selects it from the start)");
 }
 
 // Update launches that carried the point-source blocks since the last check: did block 0 give up waiting for them?
@@ -2141,7 +1954,6 @@ int lc_joint_run_sharded(lc_joint *j, int n_iter, const lc_adabelief_cfg *cfg, l
     const int rg = upd_gate_finish(j);
     if (!rc) rc = rg;
   }
-  if (!rc) rc = chain_check(j);
   if (!rc) rc = pts_tail_check(j);
   if (!rc && may_cluster && j->cl_parts_last > 0) {
     // a sharded run cannot be redone by one rank alone (the others have moved on through the same all-reduces): report it;
@@ -2607,7 +2419,6 @@ int lc_joint_run_adabelief(lc_joint *j, int n_iter, const lc_adabelief_cfg *cfg)
     const int rg = upd_gate_finish(j);
     if (!rc) rc = rg;
   }
-  if (!rc) rc = chain_check(j);
   return rc;
 }
 int lc_joint_iterations_done(lc_joint *j) { return j ? j->iters_done : LC_ERR_INVALID; }
@@ -2880,9 +2691,6 @@ int lc_joint_fisher_flux_cov(lc_joint *j, float *fisher, float *cov, float *sigm
 #ifdef LC_STAMPS
 int lc_debug_get_jstamps(long long *out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(lc::g_jstamps), 32 * sizeof(long long)) == hipSuccess ? 0 : -2;
-}
-int lc_debug_get_rstamps(long long *out) {  // (the row-block regulariser kernel: tools/rows_stamps.py)
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(lc::g_rstamps), 16 * sizeof(long long)) == hipSuccess ? 0 : -2;
 }
 int lc_debug_get_ustamps(long long *out) {  // (the fused reduction + update launch: tools/update_stamps.py)
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(lc::g_ustamps), 16 * sizeof(long long)) == hipSuccess ? 0 : -2;

@@ -1,8 +1,8 @@
-// Fourth form of the regulariser chain (default from round 4 on): the batched tiled products of joint_reg_mfma.h with the
+// Four-launch form of the regulariser chain (default from round 4 on): the batched tiled products of joint_reg_mfma.h with the
 // element-wise launches folded into them and the point-source term taken out of the products altogether - FOUR launches per
 // iteration instead of eight, seven products per launch instead of eight.
 //
-// The eight launches of the second form (Pbar, T = X AT, c = A T, S planes, T' = S A, Z = AT T', sums, values + flag) take
+// The eight launches of joint_reg_mfma.h (Pbar, T = X AT, c = A T, S planes, T' = S A, Z = AT T', sums, values + flag) take
 // 5 - 7.5 us each for 1 - 2 us of work and ~60 us per iteration at N = 128 (profiles/r04_cluster_e25_summary.txt): once the
 // epoch kernel of a shard runs as a cluster launch (42 us) the chain IS the iteration, and one launch with in-kernel syncs
 // was no shorter (59.4 us) - what shortens it is fewer stages.  The element-wise stages need no stage of their own:

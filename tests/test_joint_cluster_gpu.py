@@ -116,22 +116,3 @@ def test_a_cluster_launch_that_gives_up_is_redone_by_the_library(ctx):
     np.testing.assert_array_equal(a[0], b[0])
     for k in FREE:
         np.testing.assert_array_equal(a[1][k], b[1][k])
-
-
-@pytest.mark.parametrize('loss', [None, dict(lam_scales=1.0, lam_hf=1.0, lam_positivity=100.0),
-                                  dict(lam_positivity=100.0, lam_pts_source=0.01)])
-@pytest.mark.parametrize('cluster', ['0', '6'])
-def test_one_launch_regulariser_chain_equals_the_launches(ctx, loss, cluster):
-    """The regulariser of the 128 x 128 background grid as ONE launch (csrc/joint_reg_mfma.h, mreg_chain_kernel: the stages
-    of the launch chain separated by syncs over its 64 resident workgroups) (LCMI_REG_CHAIN=1) against the eight launches (the default):
-    same stages, same summation orders - identical bits, beside the one-workgroup epoch kernel and beside the cluster form."""
-    ds = make_roi_dataset(E=6, M=2, n=64, ss=2, seed=104)
-    T = 12
-    # (LCMI_REG_FUSED=0: the eight launches the one-launch form restates; the default since round 4 is the four-launch form of
-    #  csrc/joint_reg_fused.h, which adds its values in another order - tests/test_joint_paths_gpu.py)
-    a = _fit(ctx, ds, 2, T, env={'LCMI_CLUSTER': cluster, 'LCMI_REG_CHAIN': '0', 'LCMI_REG_FUSED': '0'}, loss=loss)
-    b = _fit(ctx, ds, 2, T, env={'LCMI_CLUSTER': cluster, 'LCMI_REG_CHAIN': '1', 'LCMI_REG_FUSED': '0'}, loss=loss)
-    np.testing.assert_array_equal(a[0], b[0])
-    for k in FREE:
-        np.testing.assert_array_equal(a[1][k], b[1][k])
-    assert a[0][-1] < a[0][0]

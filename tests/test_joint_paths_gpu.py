@@ -1,13 +1,14 @@
-"""The joint fit has two implementations of two of its steps, chosen per object at creation / per iteration:
+"""The joint fit has several implementations of some of its steps, chosen per object at creation / per iteration:
 
-* the starlet regulariser of the large background grids (N >= 128): two-sided products on the fp32 matrix cores
-  (csrc/joint_reg_mfma.h, default) or the a-trous cascade kernels (LCMI_REG_CASCADE=1);
+* the starlet regulariser of the large background grids (N >= 128): products on the fp32 matrix cores - four launches
+  (csrc/joint_reg_fused.h, default) or eight (csrc/joint_reg_mfma.h: LCMI_REG_FUSED=0, and wherever the four-launch form does
+  not apply) - or the a-trous cascade kernels (LCMI_REG_CASCADE=1, the independent cross-check);
 * inside lc_joint_run_adabelief with the background free: reduction over the epochs and update in one launch (default) or
   as two kernels (LCMI_SPLIT_UPDATE=1; the kernels the sharded drive uses); the fused launch learns that the second
   stream's regulariser is complete from a flag it checks itself (default) or from an event wait (LCMI_EVENT_SYNC=1).
 
-Both pairs compute the same numbers in different summation orders; these tests run the same fit through each and compare
-(fp32 rounding of the sums only: 1e-5 relative on the loss history, a few 1e-6 of the parameter scale on the parameters).
+The forms of a step compute the same numbers in different summation orders; these tests run the same fit through each and
+compare (fp32 rounding of the sums only: 1e-5 relative on the loss history, a few 1e-6 of the parameter scale on the parameters).
 The C5 problem at its full epoch count (1000 x 128 x 128, 4 sources; BASELINE.json configs[4]) runs here too: no oracle at
 that size, so the checks are size-independent ones (decreasing loss, determinism, epochs independent of their
 position in the batch)."""
@@ -21,7 +22,7 @@ from lightcurver_amd.synthetic import make_roi_dataset
 pytestmark = pytest.mark.gpu
 
 
-def _fit(ctx, ds, M, T, env=None, lr=1e-4, idx=None):
+def _fit(ctx, ds, M, T, env=None, lr=1e-4, idx=None, loss=None):
     from lightcurver_amd.joint import JointFit
     old = {k: os.environ.get(k) for k in (env or {})}
     os.environ.update(env or {})
@@ -37,7 +38,7 @@ def _fit(ctx, ds, M, T, env=None, lr=1e-4, idx=None):
         p['a'] = 0.9 * p['a']
         j.set_params(**p)
         W = j.propagate_noise()
-        j.set_loss(W=W, lam_scales=1.0, lam_hf=1.0, lam_positivity=100.0, lam_pts_source=0.01, lam_flux_uniformity=10.0)
+        j.set_loss(W=W, **(loss or dict(lam_scales=1.0, lam_hf=1.0, lam_positivity=100.0, lam_pts_source=0.01, lam_flux_uniformity=10.0)))
         j.set_free(['a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h'])
         j.run_adabelief(T, init_learning_rate=lr, schedule_learning_rate=False)
         out = (np.asarray(j.loss_history(), dtype=np.float64), {k: np.asarray(v, dtype=np.float64) for k, v in j.get_params().items()})
@@ -78,17 +79,14 @@ def test_matrix_core_regulariser_equals_the_cascade(ctx, E, n, M):
 
 @pytest.mark.parametrize('E,n,M', [(8, 64, 2), (3, 128, 4)])
 def test_regulariser_chain_forms_agree(ctx, E, n, M):
-    """The matrix-core regulariser of the large grids exists as batched tiled products over the scales (default; the K loop of
-    a tile only covers the band of the cumulative smoothing operator), the same with all K slices (LCMI_REG_DENSE=1: the
-    skipped slices multiply by zeros, so the bits are the same) and as the block-column kernels of round 2
-    (LCMI_REG_MFMA_V1=1: another summation order)."""
+    """The matrix-core regulariser of the large grids is batched tiled products over the scales (default; the K loop of a tile
+    only covers the band of the cumulative smoothing operator) or the same with all K slices (LCMI_REG_DENSE=1: the skipped
+    slices multiply by zeros, so the bits are the same)."""
     ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=104)
     a = _fit(ctx, ds, M, 20)
     b = _fit(ctx, ds, M, 20, env={'LCMI_REG_DENSE': '1'})
     np.testing.assert_array_equal(a[0], b[0])
     np.testing.assert_array_equal(a[1]['h'], b[1]['h'])
-    c = _fit(ctx, ds, M, 20, env={'LCMI_REG_MFMA_V1': '1'})
-    _compare(a, c, ('a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h'), 20, 1e-4)
 
 
 @pytest.mark.parametrize('E,n,M', [(8, 64, 2), (3, 128, 4), (6, 64, 1)])
@@ -110,6 +108,20 @@ def test_four_launch_chain_equals_the_eight_launch_one(ctx, E, n, M):
     a1 = _fit(ctx, ds, M, 1)
     b1 = _fit(ctx, ds, M, 1, env={'LCMI_REG_FUSED': '0'})
     np.testing.assert_array_equal(a1[1]['h'], b1[1]['h'])
+
+
+def test_eight_launch_chain_without_l1_weights_equals_the_cascade(ctx):
+    """Both l1 weights zero, positivity and the point-source term on, n = 128: the four-launch form does not apply (its values
+    ride in the products of the scales, and there are none), so the eight-launch form IS the production path - the product
+    batch of the point-source channel alone, the S plane with the positivity term, the sums.  Against the cascade, with the
+    tolerance of test_matrix_core_regulariser_equals_the_cascade."""
+    E, n, M = 3, 128, 4
+    loss = dict(lam_scales=0.0, lam_hf=0.0, lam_positivity=100.0, lam_pts_source=0.01, lam_flux_uniformity=10.0)
+    ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=104)
+    a = _fit(ctx, ds, M, 25, loss=loss)
+    b = _fit(ctx, ds, M, 25, env={'LCMI_REG_CASCADE': '1'}, loss=loss)
+    _compare(a, b, ('a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h'), 25, 1e-4)
+    assert a[0][-1] < a[0][0]
 
 
 @pytest.mark.parametrize('E,n,M', [(8, 64, 2), (5, 32, 2), (3, 128, 4)])
@@ -208,35 +220,6 @@ def test_stencil_in_the_reduction_equals_the_slab_form(ctx, E, parts):
     b = _fit(ctx, ds, 4, 12, env=dict(env, LCMI_STENCIL_REDUCE='1'))
     assert np.max(np.abs(a[0] - b[0]) / np.abs(b[0])) < 1e-6
     _compare(a, b, ('a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h'), 12, 1e-4)
-
-
-@pytest.mark.parametrize('E,n,M', [(8, 64, 2), (3, 128, 4)])
-def test_point_source_term_beside_the_chain_equals_the_batched_form(ctx, E, n, M):
-    """The point-source starlet term as tiles in one launch on a third stream beside the regulariser chain (LCMI_PTS_SIDE=1;
-    measured slower, opt-in) against the same term as one more product in each batch of the chain (default): other summation
-    order of the scale-0 stencil, same numbers to fp32 rounding."""
-    ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=104)
-    # (LCMI_EVENT_SYNC=1: this opt-in form joins a THIRD stream into the chain with events; in a process that has created many
-    #  streams before, the runtime may put two of the three onto one hardware queue, and the update's in-kernel wait for a chain
-    #  that is held up there ran out once in a full-suite run.  What is compared here is the arithmetic of the two forms.)
-    a = _fit(ctx, ds, M, 25, env={'LCMI_PTS_SIDE': '1', 'LCMI_EVENT_SYNC': '1'})
-    b = _fit(ctx, ds, M, 25)
-    _compare(a, b, ('a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h'), 25, 1e-4)
-
-
-@pytest.mark.parametrize('parts', ['2', '3'])
-def test_row_block_regulariser_equals_the_batched_products(ctx, parts):
-    """The regulariser of the 128 x 128 grid cut by rows (csrc/joint_reg_rows.h, LCMI_REG_ROWS=1: forward products, S rows and
-    adjoint products of a row block in ONE workgroup, 16 x 16 x 4 fp32 MFMA tiles with a permuted k order; the point-source
-    term as tiles) against the batched-product chain (the default) and against the cascade: same mathematics, other
-    summation orders."""
-    ds = make_roi_dataset(E=8, M=2, n=64, ss=2, seed=104)
-    a = _fit(ctx, ds, 2, 25)
-    b = _fit(ctx, ds, 2, 25, env={'LCMI_REG_ROWS': '1', 'LCMI_REG_ROWS_PARTS': parts})
-    c = _fit(ctx, ds, 2, 25, env={'LCMI_REG_CASCADE': '1'})
-    _compare(b, a, ('a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h'), 25, 1e-4)
-    _compare(b, c, ('a', 'c_x', 'c_y', 'dx', 'dy', 'mean', 'h'), 25, 1e-4)
-    assert b[0][-1] < b[0][0]
 
 
 @pytest.mark.parametrize('parts', ['2', '4'])

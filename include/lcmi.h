@@ -100,6 +100,35 @@ int lc_detect_cosmics(lc_ctx *ctx, int K, int n, const float *data, const float 
                       const uint8_t *inmask /*nullable*/, const lc_cosmics_cfg *cfg, uint8_t *crmask,
                       float *clean /*nullable*/, int32_t *iters /*nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- neighbouring sources of the star stamps: replaces sep.extract inside mask_surrounding_stars -----------
+ * Reference call site: lightcurver/processes/psf_modelling.py:45 (once per star stamp, loop at :129-133) with
+ * thresh = 3, minarea = 15, deblend_cont = 0.001 and sep's defaults deblend_nthresh = 32, clean = True, clean_param = 1.
+ * Matched filter, 8-connected groups, multi-threshold de-blending, clean and the choice of the central object as frozen
+ * in DESIGN.md §5 "Source masking": one call over K stamps gives the bits of the SPEC's restatement.
+ *   data, noisemap [K][n][n]; a pixel with non-finite data or noise, or noise <= 0, carries no weight.
+ *   mask [K][n][n]: 1 = good pixel, 0 = a pixel of any object other than the one nearest the stamp centre;
+ *   segmap [K][n][n]: pixels of object i carry i + 1, the rest 0; nobj [K]; xy [K][LC_SEGMENT_MAX_OBJECTS][2]: the
+ *   barycentres (x = column, y = row) of the objects, 0 past nobj; status [K]: 0 fine, 1 more than
+ *   LC_SEGMENT_MAX_OBJECTS objects before clean or more than 64 nodes in the de-blending trees, 2 an iteration bound
+ *   was reached, 3 a detected pixel with S/N >= 65536 (outside the fixed-point range of the sums).  A stamp with a
+ *   non-zero status has mask = 1, segmap = 0, nobj = 0, xy = 0.  kernel_ms = device time of the kernel (HIP events).
+ * Any square n from 8 to 64 (lc_segment_supported, no device needed), any K, one launch.  LC_ERR_UNSUPPORTED: n outside
+ * that range, clean_param != 1, deblend_nthresh not 4, 8, 16 or 32, minarea < 1.  LC_ERR_INVALID: thresh <= 0 or
+ * deblend_cont < 0 or either not finite. */
+#define LC_SEGMENT_MAX_OBJECTS 32
+typedef struct {
+  float thresh;            /* 3.0 */
+  int32_t minarea;         /* 15 */
+  int32_t deblend_nthresh; /* 32 */
+  float deblend_cont;      /* 0.001 */
+  float clean_param;       /* 1.0 (the only one built) */
+  int32_t clean;           /* 1 */
+} lc_segment_cfg;
+int lc_segment_supported(int n);
+int lc_segment_stamps(lc_ctx *ctx, int K, int n, const float *data, const float *noisemap, const lc_segment_cfg *cfg,
+                      uint8_t *mask, int32_t *segmap /*nullable*/, int32_t *nobj /*nullable*/, float *xy /*nullable*/,
+                      int32_t *status /*nullable*/, float *kernel_ms /*nullable*/);
+
 /* ---- optimiser settings shared by both fits ----------------------------------------------- */
 /* optax.adabelief as driven by STARRED's Optimizer(method='adabelief'):
  * lightcurver/processes/star_photometry.py:113-122, roi_modelling.py:326-334. */

@@ -46,6 +46,13 @@ class CosmicsCfg(C.Structure):
                 ('cleantype', C.c_int32), ('fsmode', C.c_int32)]
 
 
+class SegmentCfg(C.Structure):
+    _fields_ = [('thresh', C.c_float), ('minarea', C.c_int32), ('deblend_nthresh', C.c_int32),
+                ('deblend_cont', C.c_float), ('clean_param', C.c_float), ('clean', C.c_int32)]
+
+
+SEGMENT_MAX_OBJECTS = 32   # LC_SEGMENT_MAX_OBJECTS of include/lcmi.h
+
 # every symbol include/lcmi.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     'lc_version': (C.c_int, []),
@@ -59,6 +66,9 @@ SIGNATURES = {
     'lc_cosmics_supported': (C.c_int, [C.c_int]),
     'lc_detect_cosmics': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_uint8), C.POINTER(CosmicsCfg),
                                     C.POINTER(C.c_uint8), fp, ip, C.POINTER(C.c_float)]),
+    'lc_segment_supported': (C.c_int, [C.c_int]),
+    'lc_segment_stamps': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, C.POINTER(SegmentCfg), C.POINTER(C.c_uint8), ip, ip, fp,
+                                    ip, C.POINTER(C.c_float)]),
     'lc_ctx_stream': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     'lc_ctx_synchronize': (C.c_int, [vp]),
     'lc_timer_start': (C.c_int, [vp]),

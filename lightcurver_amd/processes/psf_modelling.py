@@ -28,6 +28,38 @@ def mask_surrounding_stars(data, noisemap, thresh=3.0, minarea=15, deblend_cont=
     return mask
 
 
+def mask_surrounding_stars_batch(datas, noisemaps, thresh=3.0, minarea=15, deblend_cont=0.001, ctx=None):
+    """``mask_surrounding_stars`` for every stamp at once on the device (``lc_segment_stamps``; the loop of
+    psf_modelling.py:129-133 as one call).  datas, noisemaps: a (K, n, n) stack each, or equal-length lists of square
+    stamps whose sizes may differ (one device call per size).  Returns (masks, n_host): boolean masks, True = good
+    pixel, as a (K, n, n) array for a stack and as a list otherwise; n_host counts the stamps that went through the
+    host ``mask_surrounding_stars`` instead: those larger than 64 pixels and those the device reported (table full,
+    iteration bound, value outside the fixed-point range)."""
+    from .source_masking import segment_batch
+    stack = isinstance(datas, np.ndarray) and datas.ndim == 3
+    ds = [np.asarray(c, dtype=np.float32) for c in datas]
+    ns = [np.asarray(m, dtype=np.float32) for m in noisemaps]
+    if len(ds) != len(ns):
+        raise ValueError('one noise map per stamp')
+    kw = dict(thresh=thresh, minarea=minarea, deblend_cont=deblend_cont)
+    out, n_host = [None] * len(ds), 0
+    for shape in sorted({c.shape for c in ds}):
+        idx = [i for i, c in enumerate(ds) if c.shape == shape]
+        if len(shape) != 2 or shape[0] != shape[1]:
+            raise ValueError(f'square stamps expected, got {shape}')
+        if shape[0] > 64:
+            todo = idx
+        else:
+            r = segment_batch(np.stack([ds[i] for i in idx]), np.stack([ns[i] for i in idx]), ctx=ctx, **kw)
+            for i, m in zip(idx, r['mask']):
+                out[i] = m
+            todo = [i for i, st in zip(idx, r['status']) if st != 0]
+        for i in todo:
+            out[i] = mask_surrounding_stars(ds[i], ns[i], **kw)
+        n_host += len(todo)
+    return (np.stack(out) if stack and out else out), n_host
+
+
 def prepare_psf_stamps(datas, noisemaps, cosmics_masks, automatic_masks=None, mask_threshold_fraction=0.4):
     """Masks and clean-up of one frame's star stamps.
 
@@ -95,11 +127,25 @@ def relative_loss_differential(loss_history):
 
 
 def model_psfs_of_frames(frames, subsampling_factor=2, psf_n_iter_analytic=100, psf_n_iter_pixels=3000,
-                         field_distortion=False, **build_kwargs):
+                         field_distortion=False, mask_neighbours=False, **build_kwargs):
     """frames: iterable of dicts with 'datas', 'noisemaps', 'cosmics_masks' (and optionally
     'automatic_masks', 'seeing_pixels', 'pixel_scale', 'id').  Frames whose stamps are all rejected are
     skipped (psf_modelling.py:154-160).  Returns a list of (frame, result-or-None) with the quantities the
-    reference stores: narrow_psf, full_psf, chi2, relative_loss_differential, fwhm_moffat_pixels."""
+    reference stores: narrow_psf, full_psf, chi2, relative_loss_differential, fwhm_moffat_pixels.
+    mask_neighbours=True: every frame that brings no 'automatic_masks' gets them from one batched device call over the
+    stamps of all such frames (mask_surrounding_stars_batch, the reference's psf_modelling.py:129-133)."""
+    given = frames = list(frames)
+    if mask_neighbours:
+        frames = list(frames)
+        todo = [k for k, fr in enumerate(frames) if fr.get('automatic_masks') is None and len(fr['datas'])]
+        if todo:
+            masks, _ = mask_surrounding_stars_batch([d for k in todo for d in frames[k]['datas']],
+                                                    [m for k in todo for m in frames[k]['noisemaps']])
+            o = 0
+            for k in todo:
+                sz = len(frames[k]['datas'])
+                frames[k] = dict(frames[k], automatic_masks=np.stack(masks[o:o + sz]))
+                o += sz
     prepared, index = [], []
     cleaned = prepare_psf_stamps_batched(frames)
     for k, fr in enumerate(frames):
@@ -108,7 +154,7 @@ def model_psfs_of_frames(frames, subsampling_factor=2, psf_n_iter_analytic=100, 
             continue
         prepared.append((d, nmap, m, float(fr.get('seeing_pixels', 3.0)), keep))
         index.append(k)
-    out = [(fr, None) for fr in frames]
+    out = [(fr, None) for fr in given]
     if not prepared:
         return out
     results = build_psf_batch([p[0] for p in prepared], [p[1] for p in prepared], subsampling_factor,
@@ -121,5 +167,5 @@ def model_psfs_of_frames(frames, subsampling_factor=2, psf_n_iter_analytic=100, 
         res['fwhm_moffat_pixels'] = float((0.5 * (km['fwhm_x'] + km['fwhm_y'])).item())
         res['relative_loss_differential'] = relative_loss_differential(res['adabelief_extra_fields']['loss_history'])
         res['stars_kept'] = p[4]
-        out[k] = (frames[k], res)
+        out[k] = (given[k], res)
     return out

@@ -170,3 +170,59 @@ def extract(data, noisemap, thresh=3.0, minarea=15, deblend_nthresh=32, deblend_
         seg[m] = len(objs)
     objects = np.array(objs, dtype=[('x', 'f8'), ('y', 'f8'), ('npix', 'i4'), ('flux', 'f8')])
     return objects, seg
+
+
+def segment_batch(datas, noisemaps, thresh=3.0, minarea=15, deblend_nthresh=32, deblend_cont=0.001,
+                  clean_detections=True, clean_param=1.0, ctx=None):
+    """The device form of ``extract`` over a (K, n, n) stack, n from 8 to 64: one call of ``lc_segment_stamps``
+    (include/lcmi.h), the SPEC of DESIGN.md §5 "Source masking".  Returns dict(mask bool (K, n, n), True = good pixel:
+    everything but the objects that are not the central one; segmap int32; nobj int32 (K,); xy float32 (K, 32, 2)
+    barycentres; status int32 (K,), non-zero = not segmented (all-good mask); kernel_ms).  There is no CPU fallback."""
+    import ctypes as C
+    from .. import _lib
+    ctx = ctx or _lib.default_context()
+    lib = _lib.lib()
+    d, s = _lib.f32(datas), _lib.f32(noisemaps)
+    if d.ndim != 3 or d.shape[1] != d.shape[2] or s.shape != d.shape:
+        raise ValueError(f'expected two (K, n, n) stacks of square stamps, got {d.shape} and {s.shape}')
+    K, n = d.shape[0], d.shape[1]
+    if not lib.lc_segment_supported(n):
+        raise _lib.LcError(f'lc_segment_stamps takes stamps of 8 .. 64 pixels, not {n}')
+    cfg = _lib.SegmentCfg(float(thresh), int(minarea), int(deblend_nthresh), float(deblend_cont), float(clean_param),
+                          int(bool(clean_detections)))
+    mask = np.ones(d.shape, np.uint8)
+    seg = np.zeros(d.shape, np.int32)
+    nobj = np.zeros(K, np.int32)
+    status = np.zeros(K, np.int32)
+    xy = np.zeros((K, _lib.SEGMENT_MAX_OBJECTS, 2), np.float32)
+    ms = C.c_float()
+    i32 = C.POINTER(C.c_int32)
+    if K:
+        ctx.check(lib.lc_segment_stamps(ctx.h, K, n, _lib.ptr(d), _lib.ptr(s), C.byref(cfg),
+                                        mask.ctypes.data_as(C.POINTER(C.c_uint8)), seg.ctypes.data_as(i32),
+                                        nobj.ctypes.data_as(i32), _lib.ptr(xy), status.ctypes.data_as(i32), C.byref(ms)),
+                  'lc_segment_stamps')
+    return dict(mask=mask.astype(bool), segmap=seg, nobj=nobj, xy=xy, status=status, kernel_ms=ms.value)
+
+
+def extract_batch(datas, noisemaps, thresh=3.0, minarea=15, deblend_nthresh=32, deblend_cont=0.001, clean_detections=True,
+                  clean_param=1.0, ctx=None):
+    """``extract`` for every stamp of a (K, n, n) stack in one device call: a list of (objects, segmentation map) pairs
+    with the fields and conventions of ``extract`` ('x', 'y' the device's float32 barycentres; 'npix' and 'flux' summed
+    over the map here).  A stamp the device reports (non-zero status) comes back as None."""
+    r = segment_batch(datas, noisemaps, thresh, minarea, deblend_nthresh, deblend_cont, clean_detections, clean_param, ctx)
+    d = np.asarray(datas, dtype=np.float64)
+    out = []
+    for k in range(len(d)):
+        if r['status'][k] != 0:
+            out.append(None)
+            continue
+        m, seg = int(r['nobj'][k]), r['segmap'][k]
+        objects = np.zeros(m, dtype=[('x', 'f8'), ('y', 'f8'), ('npix', 'i4'), ('flux', 'f8')])
+        objects['x'], objects['y'] = r['xy'][k, :m, 0], r['xy'][k, :m, 1]
+        if m:
+            idx = np.arange(1, m + 1)
+            objects['npix'] = ndimage.sum(np.ones(seg.shape), seg, idx)
+            objects['flux'] = ndimage.sum(np.where(np.isfinite(d[k]), d[k], 0.0), seg, idx)
+        out.append((objects, seg))
+    return out

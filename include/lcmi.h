@@ -129,6 +129,32 @@ int lc_segment_stamps(lc_ctx *ctx, int K, int n, const float *data, const float 
                       uint8_t *mask, int32_t *segmap /*nullable*/, int32_t *nobj /*nullable*/, float *xy /*nullable*/,
                       int32_t *status /*nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- alignment and stacking of the ROI epochs (the reference's stack_data_diagnostic, roi_modelling.py:34-125) ---------------
+ * Align: every epoch e of every cube goes through scipy's rotate(shift(img, shift_yx[e]), angle_deg[e], reshape=False) with
+ *   scipy's defaults: cubic B-spline prefilter (pole sqrt(3) - 2, whole-sample mirror boundaries), resample with 4 x 4
+ *   taps, 0 where the coordinate leaves [0, n - 1]; twice, once per step (DESIGN.md section 5 "Align and stack").
+ *   Coordinates and the in-range test in double, weights and sums in float.  shift_yx = (-dy, -dx) of the fit, angle = alpha.
+ *   shift_yx and angle_deg both NULL: no alignment, the cubes are stacked as they are.
+ * Stack: per pixel over the epochs whose (aligned) value is finite: median (exact order statistic, 0.5 (lo + hi) for an even
+ *   count), standard deviation (ddof 0, two passes), epoch kept if |v - median| <= n_sigma * deviation or the deviation is
+ *   not finite, stack = sum w v / sum w with w = 1 / noisemap over the kept epochs (the noise map as given, not aligned; 0 / 0
+ *   = NaN).  clip = 0: every finite epoch is kept.  n_rejected: finite epochs the clip dropped.
+ * Any output may be NULL; noisemap may be NULL when stack and n_rejected are; cfg NULL = {3.0, 1}.  kernel_ms = device time
+ * of both kernels (HIP events).  Any square n from 8 to 128 (lc_align_stack_supported, no device needed; LC_ERR_UNSUPPORTED
+ * otherwise), any C <= 65535, any E.  LC_ERR_INVALID: C or E < 1, a non-finite shift or angle, n_sigma <= 0 or not finite,
+ * only one of shift_yx and angle_deg given. */
+typedef struct {
+  float n_sigma; /* 3.0 */
+  int32_t clip;  /* 1 = one rejection pass, 0 = plain weighted mean */
+} lc_stack_cfg;
+int lc_align_stack_supported(int n);
+int lc_align_stack(lc_ctx *ctx, int C, int E, int n, const float *cubes /* [C][E][n][n] */,
+                   const float *noisemap /* [E][n][n], shared by the C cubes */,
+                   const double *shift_yx /* [E][2] */, const double *angle_deg /* [E] */, const lc_stack_cfg *cfg,
+                   float *aligned /* nullable [C][E][n][n] */, float *stack /* nullable [C][n][n] */,
+                   float *median /* nullable [C][n][n] */, int32_t *n_rejected /* nullable [C][n][n] */,
+                   float *kernel_ms /* nullable */);
+
 /* ---- optimiser settings shared by both fits ----------------------------------------------- */
 /* optax.adabelief as driven by STARRED's Optimizer(method='adabelief'):
  * lightcurver/processes/star_photometry.py:113-122, roi_modelling.py:326-334. */

@@ -51,6 +51,10 @@ class SegmentCfg(C.Structure):
                 ('deblend_cont', C.c_float), ('clean_param', C.c_float), ('clean', C.c_int32)]
 
 
+class StackCfg(C.Structure):
+    _fields_ = [('n_sigma', C.c_float), ('clip', C.c_int32)]
+
+
 SEGMENT_MAX_OBJECTS = 32   # LC_SEGMENT_MAX_OBJECTS of include/lcmi.h
 
 # every symbol include/lcmi.h declares: name -> (restype, argtypes)
@@ -69,6 +73,9 @@ SIGNATURES = {
     'lc_segment_supported': (C.c_int, [C.c_int]),
     'lc_segment_stamps': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, C.POINTER(SegmentCfg), C.POINTER(C.c_uint8), ip, ip, fp,
                                     ip, C.POINTER(C.c_float)]),
+    'lc_align_stack_supported': (C.c_int, [C.c_int]),
+    'lc_align_stack': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, dp, dp, C.POINTER(StackCfg), fp, fp, fp, ip,
+                                 C.POINTER(C.c_float)]),
     'lc_ctx_stream': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     'lc_ctx_synchronize': (C.c_int, [vp]),
     'lc_timer_start': (C.c_int, [vp]),

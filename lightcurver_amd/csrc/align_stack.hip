@@ -1,0 +1,364 @@
+// Alignment and stacking of the ROI epochs: what stack_data_diagnostic (lightcurver/processes/roi_modelling.py:34-125)
+// does with scipy.ndimage.shift, scipy.ndimage.rotate and a sigma-clipped weighted mean, frozen as the SPEC of
+// DESIGN.md §5 "Align and stack".  Two kernels on the context's stream:
+//
+//   align  one workgroup per (cube, epoch), two fp32 planes in LDS (row stride n | 1: a lane per row and a lane per
+//          column both walk conflict-free banks).  Cubic B-spline prefilter (a lane per line, columns then rows),
+//          resample at the shift's coordinates into the second plane, prefilter again, resample at the rotation's
+//          coordinates back into the first, coalesced write.  Coordinates and the in-range test in double.
+//   stack  one lane per (cube, pixel), adjacent lanes adjacent pixels, so every read of an epoch is coalesced.  The
+//          median is the exact order statistic: bitwise bisection on the order-preserving integer key of the float, 32
+//          counting passes over the epochs, both middle elements at once.  Mean, deviation, rejection and the weighted
+//          mean are sequential sums in epoch order: the result does not depend on the launch.
+#pragma clang fp contract(off)  // the SPEC fixes every rounding, and the coordinates are scipy's own expressions
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "lc_common.h"
+#include "../../include/lcmi.h"
+
+namespace lc {
+
+constexpr int kAlThreads = 256;
+constexpr int kStThreads = 64;
+constexpr int kAlMinN = 8, kAlMaxN = 128;
+constexpr int kAlHorizon = 32;  // terms of the causal initial sum: |z|^32 = 5e-19, below the floor of either precision
+constexpr int kAlGeo = 8;       // doubles per epoch: s_y, s_x, m00, m01, m10, m11, off_y, off_x
+
+__host__ __device__ constexpr int al_ld(int n) { return n | 1; }
+__host__ __device__ constexpr size_t al_lds_bytes(int n) { return (size_t)2 * n * al_ld(n) * sizeof(float); }
+
+struct AlignArgs {
+  int n;
+  float pole, gain, den, last;  // z, 6, 1 - z^(2n-2), z / (z^2 - 1)
+  const float *in;
+  float *out;
+  const double *geo;  // [E][kAlGeo]
+  int E;
+};
+
+// One line of n samples, `s` floats apart: c <- its cubic B-spline coefficients (whole-sample mirror boundaries).
+__device__ __forceinline__ void al_prefilter_line(float *c, int s, int n, const AlignArgs &A) {
+  const float z = A.pole, g = A.gain;
+  const int K = min(2 * n - 2, kAlHorizon);
+  float zk = 1.0f, sum = 0.0f;
+  for (int k = 0; k < K; ++k) {
+    const int i = k < n ? k : 2 * n - 2 - k;
+    sum = sum + zk * (g * c[i * s]);
+    zk = zk * z;
+  }
+  float prev = sum / A.den, before = prev;
+  c[0] = prev;
+  for (int i = 1; i < n; ++i) {
+    before = prev;
+    prev = g * c[i * s] + z * prev;
+    c[i * s] = prev;
+  }
+  float nxt = A.last * (prev + z * before);
+  c[(n - 1) * s] = nxt;
+  for (int i = n - 2; i >= 0; --i) {
+    nxt = z * (nxt - c[i * s]);
+    c[i * s] = nxt;
+  }
+}
+
+__device__ __forceinline__ void al_prefilter(float *P, int n, int ld, const AlignArgs &A) {
+  const int tid = threadIdx.x;
+  if (tid < n) al_prefilter_line(P + tid, ld, n, A);  // column tid: lanes on adjacent banks
+  __syncthreads();
+  if (tid < n) al_prefilter_line(P + tid * ld, 1, n, A);  // row tid: lanes ld (odd) banks apart
+  __syncthreads();
+}
+
+__device__ __forceinline__ void al_weights(float t, float w[4]) {
+  const float u = 1.0f - t;
+  w[1] = (t * t * (t - 2.0f) * 3.0f + 4.0f) / 6.0f;
+  w[2] = (u * u * (u - 2.0f) * 3.0f + 4.0f) / 6.0f;
+  w[0] = u * u * u / 6.0f;
+  w[3] = 1.0f - w[0] - w[1] - w[2];
+}
+
+__device__ __forceinline__ int al_mirror(int i, int n) {
+  if (i < 0) i = -i;
+  if (i > n - 1) i = 2 * (n - 1) - i;
+  return i;
+}
+
+// dst(y, x) = the spline with coefficients src at (m00 y + m01 x + oy, m10 y + m11 x + ox), 0 outside [0, n - 1].
+__device__ __forceinline__ void al_resample(const float *src, float *dst, int n, int ld, double m00, double m01,
+                                            double m10, double m11, double oy, double ox, bool diagonal) {
+  const int np = n * n;
+  const double hi = (double)(n - 1);
+  for (int p = threadIdx.x; p < np; p += kAlThreads) {
+    const int y = p / n, x = p - y * n;
+    double cy, cx;
+    if (diagonal) {  // scipy's shift: index + offset, per axis
+      cy = (double)y + oy;
+      cx = (double)x + ox;
+    } else {  // scipy's affine transform: offset + sum of matrix * index, in this order
+      cy = oy + (double)y * m00;
+      cy = cy + (double)x * m01;
+      cx = ox + (double)y * m10;
+      cx = cx + (double)x * m11;
+    }
+    float v = 0.0f;
+    if (cy >= 0.0 && cy <= hi && cx >= 0.0 && cx <= hi) {
+      const double fy = floor(cy), fx = floor(cx);
+      float wy[4], wx[4];
+      al_weights((float)(cy - fy), wy);
+      al_weights((float)(cx - fx), wx);
+      const int y0 = (int)fy - 1, x0 = (int)fx - 1;
+      int xi[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) xi[b] = al_mirror(x0 + b, n);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const float *row = src + al_mirror(y0 + a, n) * ld;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          float t = row[xi[b]];
+          t = t * wy[a];
+          t = t * wx[b];
+          v = v + t;
+        }
+      }
+    }
+    dst[y * ld + x] = v;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kAlThreads) void align_kernel(AlignArgs A) {
+  extern __shared__ __align__(16) float al_lds[];
+  const int n = A.n, ld = al_ld(n), np = n * n, tid = threadIdx.x;
+  float *P0 = al_lds, *P1 = al_lds + n * ld;
+  const size_t off = (size_t)blockIdx.x * np;
+  const double *g = A.geo + (size_t)(blockIdx.x % A.E) * kAlGeo;
+  for (int p = tid; p < np; p += kAlThreads) {
+    const int y = p / n, x = p - y * n;
+    P0[y * ld + x] = A.in[off + p];
+  }
+  __syncthreads();
+  al_prefilter(P0, n, ld, A);
+  al_resample(P0, P1, n, ld, 1.0, 0.0, 0.0, 1.0, -g[0], -g[1], true);
+  al_prefilter(P1, n, ld, A);
+  al_resample(P1, P0, n, ld, g[2], g[3], g[4], g[5], g[6], g[7], false);
+  for (int p = tid; p < np; p += kAlThreads) {
+    const int y = p / n, x = p - y * n;
+    A.out[off + p] = P0[y * ld + x];
+  }
+}
+
+struct StackArgs {
+  int E, np, clip;
+  float n_sigma;
+  const float *v;      // [C][E][np]
+  const float *noise;  // [E][np]
+  float *stack, *median;
+  int32_t *nrej;
+};
+
+__device__ __forceinline__ unsigned st_key(float v) {
+  const unsigned u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float st_unkey(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+__global__ __launch_bounds__(kStThreads) void stack_kernel(StackArgs A) {
+  const int p = blockIdx.x * kStThreads + threadIdx.x, c = blockIdx.y;
+  if (p >= A.np) return;
+  const size_t np = (size_t)A.np;
+  const int E = A.E;
+  const float *v = A.v + (size_t)c * E * np + p;
+  const size_t o = (size_t)c * np + p;
+  int m = 0;
+  float s = 0.0f;
+  for (int e = 0; e < E; ++e) {
+    const float x = v[e * np];
+    if (__builtin_isfinite(x)) {
+      ++m;
+      s = s + x;
+    }
+  }
+  float med = __builtin_nanf("");
+  if (m > 0) {
+    const int klo = (m - 1) / 2, khi = m / 2;
+    unsigned tlo = 0u, thi = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned clo = tlo | (1u << bit), chi = thi | (1u << bit);
+      int nlo = 0, nhi = 0;
+      for (int e = 0; e < E; ++e) {
+        const float x = v[e * np];
+        if (__builtin_isfinite(x)) {
+          const unsigned k = st_key(x);
+          nlo += k < clo;
+          nhi += k < chi;
+        }
+      }
+      if (nlo <= klo) tlo = clo;
+      if (nhi <= khi) thi = chi;
+    }
+    const float lo = st_unkey(tlo), hi = st_unkey(thi);
+    med = klo == khi ? lo : 0.5f * (lo + hi);
+  }
+  if (A.median) A.median[o] = med;
+  if (!A.stack && !A.nrej) return;
+  const float mean = s / (float)m;
+  float q = 0.0f;
+  for (int e = 0; e < E; ++e) {
+    const float x = v[e * np];
+    if (__builtin_isfinite(x)) {
+      const float d = x - mean;
+      q = q + d * d;
+    }
+  }
+  const float dev = sqrtf(q / (float)m), thr = A.n_sigma * dev;
+  const bool all = !A.clip || !__builtin_isfinite(dev);
+  const float *noise = A.noise + p;
+  float sw = 0.0f, swv = 0.0f;
+  int rej = 0;
+  for (int e = 0; e < E; ++e) {
+    const float x = v[e * np];
+    if (!__builtin_isfinite(x)) continue;
+    if (all || fabsf(x - med) <= thr) {
+      const float w = 1.0f / noise[e * np];
+      sw = sw + w;
+      swv = swv + w * x;
+    } else {
+      ++rej;
+    }
+  }
+  if (A.stack) A.stack[o] = swv / sw;
+  if (A.nrej) A.nrej[o] = rej;
+}
+
+}  // namespace lc
+
+using namespace lc;
+
+extern "C" {
+
+int lc_align_stack_supported(int n) { return n >= kAlMinN && n <= kAlMaxN ? 1 : 0; }
+
+int lc_align_stack(lc_ctx *ctx, int C, int E, int n, const float *cubes, const float *noisemap, const double *shift_yx,
+                   const double *angle_deg, const lc_stack_cfg *cfg, float *aligned, float *stack, float *median,
+                   int32_t *n_rejected, float *kernel_ms) {
+  if (!ctx) return LC_ERR_INVALID;
+  if (!lc_align_stack_supported(n)) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_align_stack: stamp size outside 8 .. 128");
+  if (C < 1 || C > 65535 || E < 1 || !cubes) LC_FAIL(ctx, LC_ERR_INVALID, "lc_align_stack: invalid argument");
+  if ((shift_yx == nullptr) != (angle_deg == nullptr))
+    LC_FAIL(ctx, LC_ERR_INVALID, "lc_align_stack: shift_yx and angle_deg are given or left out together");
+  const bool align = shift_yx != nullptr, weighted = stack || n_rejected, stacked = weighted || median;
+  if (weighted && !noisemap) LC_FAIL(ctx, LC_ERR_INVALID, "lc_align_stack: stack and n_rejected need the noise map");
+  lc_stack_cfg cf = {3.0f, 1};
+  if (cfg) cf = *cfg;
+  if (!(cf.n_sigma > 0.f) || !std::isfinite(cf.n_sigma))
+    LC_FAIL(ctx, LC_ERR_INVALID, "lc_align_stack: n_sigma must be positive and finite");
+  std::vector<double> geo;
+  if (align) {
+    geo.resize((size_t)E * kAlGeo);
+    const double ctr = (double)(n - 1) / 2.0;
+    for (int e = 0; e < E; ++e) {
+      const double sy = shift_yx[2 * e], sx = shift_yx[2 * e + 1], ang = angle_deg[e];
+      if (!std::isfinite(sy) || !std::isfinite(sx) || !std::isfinite(ang))
+        LC_FAIL(ctx, LC_ERR_INVALID, "lc_align_stack: shifts and angles must be finite");
+      const double rad = ang * (M_PI / 180.0), co = std::cos(rad), si = std::sin(rad);
+      double *g = &geo[(size_t)e * kAlGeo];
+      g[0] = sy;
+      g[1] = sx;
+      g[2] = co;
+      g[3] = si;
+      g[4] = -si;
+      g[5] = co;
+      g[6] = ctr - (co * ctr + si * ctr);
+      g[7] = ctr - (-si * ctr + co * ctr);
+    }
+  }
+  LC_ENTER(ctx);
+  const size_t np = (size_t)n * n, tot = (size_t)C * E * np;
+  std::vector<void *> dev;
+  auto cleanup = [&]() {
+    for (void *p : dev) (void)hipFree(p);
+  };
+  auto alloc = [&](size_t bytes, void **d) -> hipError_t {
+    hipError_t e = hipMalloc(d, bytes);
+    if (e == hipSuccess) dev.push_back(*d);
+    return e;
+  };
+#define AL_TRY(call)                                              \
+  do {                                                            \
+    hipError_t e_ = (call);                                       \
+    if (e_ != hipSuccess) {                                       \
+      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+      cleanup();                                                  \
+      return LC_ERR_DEVICE;                                       \
+    }                                                             \
+  } while (0)
+  void *d_in = nullptr, *d_al = nullptr, *d_geo = nullptr, *d_noise = nullptr, *d_stack = nullptr, *d_med = nullptr,
+       *d_rej = nullptr;
+  AL_TRY(alloc(tot * 4, &d_in));
+  AL_TRY(hipMemcpyAsync(d_in, cubes, tot * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (align) {
+    AL_TRY(alloc(tot * 4, &d_al));
+    AL_TRY(alloc(geo.size() * sizeof(double), &d_geo));
+    AL_TRY(hipMemcpyAsync(d_geo, geo.data(), geo.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (weighted) {
+    AL_TRY(alloc((size_t)E * np * 4, &d_noise));
+    AL_TRY(hipMemcpyAsync(d_noise, noisemap, (size_t)E * np * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (stack) AL_TRY(alloc((size_t)C * np * 4, &d_stack));
+  if (median) AL_TRY(alloc((size_t)C * np * 4, &d_med));
+  if (n_rejected) AL_TRY(alloc((size_t)C * np * 4, &d_rej));
+  const size_t lds_bytes = al_lds_bytes(n);
+  if (align)
+    AL_TRY(hipFuncSetAttribute((const void *)align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  AL_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  if (align) {
+    const double zd = std::sqrt(3.0) - 2.0;
+    AlignArgs A;
+    A.n = n;
+    A.pole = (float)zd;
+    A.gain = 6.0f;
+    A.den = (float)(1.0 - std::pow(zd, (double)(2 * n - 2)));
+    A.last = (float)(zd / (zd * zd - 1.0));
+    A.in = (const float *)d_in;
+    A.out = (float *)d_al;
+    A.geo = (const double *)d_geo;
+    A.E = E;
+    hipLaunchKernelGGL(align_kernel, dim3((unsigned)((size_t)C * E)), dim3(kAlThreads), lds_bytes, ctx->stream, A);
+    AL_TRY(hipGetLastError());
+  }
+  const void *d_val = align ? d_al : d_in;
+  if (stacked) {
+    StackArgs S;
+    S.E = E;
+    S.np = (int)np;
+    S.clip = cf.clip != 0;
+    S.n_sigma = cf.n_sigma;
+    S.v = (const float *)d_val;
+    S.noise = (const float *)d_noise;
+    S.stack = (float *)d_stack;
+    S.median = (float *)d_med;
+    S.nrej = (int32_t *)d_rej;
+    hipLaunchKernelGGL(stack_kernel, dim3((unsigned)((np + kStThreads - 1) / kStThreads), (unsigned)C), dim3(kStThreads),
+                       0, ctx->stream, S);
+    AL_TRY(hipGetLastError());
+  }
+  AL_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  if (aligned) AL_TRY(hipMemcpyAsync(aligned, d_val, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (stack) AL_TRY(hipMemcpyAsync(stack, d_stack, (size_t)C * np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (median) AL_TRY(hipMemcpyAsync(median, d_med, (size_t)C * np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (n_rejected) AL_TRY(hipMemcpyAsync(n_rejected, d_rej, (size_t)C * np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  AL_TRY(hipStreamSynchronize(ctx->stream));
+  if (kernel_ms) AL_TRY(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+  cleanup();
+#undef AL_TRY
+  return LC_OK;
+}
+
+}  // extern "C"

@@ -277,14 +277,86 @@ def sigma_clipped_weighted_stack(data, noisemap, n_sigma=3.0):
         return np.nansum(w * np.nan_to_num(data), axis=0) / np.sum(w, axis=0)
 
 
-def stack_data_diagnostic(data, noisemap, starred_kwargs, starred_model):
+def align_stack_batch(cubes, noisemap=None, shift_yx=None, angle_deg=None, n_sigma=3.0, clip=True, want=('stack',),
+                      ctx=None):
+    """One call of ``lc_align_stack`` (include/lcmi.h; the SPEC of DESIGN.md §5 "Align and stack") on C cubes (C, E, n, n),
+    8 <= n <= 128, that share a noise map (E, n, n).  shift_yx (E, 2) and angle_deg (E,): scipy's ``shift`` and ``rotate``
+    arguments per epoch; both None: no alignment.  want: which of 'aligned' (C, E, n, n), 'stack', 'median' (C, n, n) float32
+    and 'n_rejected' (C, n, n) int32 to compute and return, next to 'kernel_ms'.  There is no CPU fallback."""
+    import ctypes as C
+    from .. import _lib
+    ctx = ctx or _lib.default_context()
+    lib = _lib.lib()
+    v = _lib.f32(cubes)
+    if v.ndim != 4 or v.shape[2] != v.shape[3]:
+        raise ValueError(f'expected (C, E, n, n) cubes of square stamps, got {v.shape}')
+    nc, E, n = v.shape[0], v.shape[1], v.shape[2]
+    unknown = set(want) - {'aligned', 'stack', 'median', 'n_rejected'}
+    if unknown:
+        raise ValueError(f'unknown outputs {sorted(unknown)}')
+    s = None
+    if noisemap is not None:
+        s = _lib.f32(noisemap)
+        if s.shape != v.shape[1:]:
+            raise ValueError(f'the noise map must be (E, n, n) = {v.shape[1:]}, got {s.shape}')
+    sh = ang = None
+    if shift_yx is not None or angle_deg is not None:
+        sh = np.ascontiguousarray(shift_yx, dtype=np.float64)
+        ang = np.ascontiguousarray(angle_deg, dtype=np.float64)
+        if sh.shape != (E, 2) or ang.shape != (E,):
+            raise ValueError(f'expected shifts (E, 2) and angles (E,), got {sh.shape} and {ang.shape}')
+    out = {}
+    if 'aligned' in want:
+        out['aligned'] = np.empty(v.shape, np.float32)
+    for name in ('stack', 'median'):
+        if name in want:
+            out[name] = np.empty((nc, n, n), np.float32)
+    if 'n_rejected' in want:
+        out['n_rejected'] = np.empty((nc, n, n), np.int32)
+    cfg = _lib.StackCfg(float(n_sigma), int(bool(clip)))
+    ms = C.c_float()
+    dptr = lambda a: None if a is None else a.ctypes.data_as(_lib.dp)
+    rej = out.get('n_rejected')
+    ctx.check(lib.lc_align_stack(ctx.h, nc, E, n, _lib.ptr(v), _lib.ptr(s), dptr(sh), dptr(ang), C.byref(cfg),
+                                 _lib.ptr(out.get('aligned')), _lib.ptr(out.get('stack')), _lib.ptr(out.get('median')),
+                                 None if rej is None else rej.ctypes.data_as(_lib.ip), C.byref(ms)), 'lc_align_stack')
+    out['kernel_ms'] = ms.value
+    return out
+
+
+def _alignment_of(starred_kwargs):
+    """scipy's arguments of ``align_data_interpolation`` per epoch: shift (-dy, -dx), rotation +alpha degrees."""
+    ka = starred_kwargs['kwargs_analytic']
+    dx, dy = np.asarray(ka['dx'], dtype=np.float64), np.asarray(ka['dy'], dtype=np.float64)
+    return np.stack([-dy, -dx], axis=1), np.asarray(ka['alpha'], dtype=np.float64)
+
+
+def align_data_interpolation_batch(arrays, starred_kwargs, ctx=None):
+    """``align_data_interpolation`` of every (E, n, n) cube of ``arrays`` (C, E, n, n) in one device call (float32)."""
+    shift_yx, angle = _alignment_of(starred_kwargs)
+    return align_stack_batch(arrays, None, shift_yx, angle, want=('aligned',), ctx=ctx)['aligned']
+
+
+def median_stack_batch(cubes, ctx=None):
+    """np.nanmedian over the epochs of every (E, n, n) cube of ``cubes`` (C, E, n, n) on the device (float32, exact order
+    statistics; an infinite sample counts as missing, like a NaN): what ``_median_stack`` computes on the host."""
+    return align_stack_batch(cubes, want=('median',), ctx=ctx)['median']
+
+
+def stack_data_diagnostic(data, noisemap, starred_kwargs, starred_model, on_device=False, ctx=None):
     """Three aligned stacks: the data, the data minus the point sources, the data minus the background
-    (reference roi_modelling.py:86-125).  Two extra forward models on the device, the rest on the host."""
+    (reference roi_modelling.py:86-125).  Two extra forward models on the device; alignment and stacking on the host, or
+    with ``on_device`` in one ``lc_align_stack`` call over the three cubes (float32 stacks, no CPU fallback)."""
     only_ps = deepcopy(starred_kwargs)
     only_ps['kwargs_background']['h'] = np.array(only_ps['kwargs_background']['h']) * 0.0
     no_ps = deepcopy(starred_kwargs)
     no_ps['kwargs_analytic']['a'] = np.array(no_ps['kwargs_analytic']['a']) * 0.0
     data = np.asarray(data, dtype=np.float64)
+    if on_device:
+        cubes = np.stack([data, data - starred_model.model(only_ps), data - starred_model.model(no_ps)])
+        shift_yx, angle = _alignment_of(starred_kwargs)
+        st = align_stack_batch(cubes, noisemap, shift_yx, angle, want=('stack',), ctx=ctx)['stack']
+        return {'stack': st[0], 'stack_no_ps': st[1], 'stack_no_background': st[2]}
     minus_ps = align_data_interpolation(data - starred_model.model(only_ps), only_ps)
     minus_bg = align_data_interpolation(data - starred_model.model(no_ps), no_ps)
     aligned = align_data_interpolation(data, starred_kwargs)

@@ -553,10 +553,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               }
             }
           }
-          chi = wave_sum(chi);
-          ga = wave_sum(ga);
-          gy = wave_sum(gy);
-          gs = wave_sum(gs);
+          wave_sum4(chi, ga, gy, gs);
           if (lane == 0) {
             float *r = RED + (s * NBLK + blk) * 5;
             r[0] = chi;

@@ -72,13 +72,18 @@ __device__ __forceinline__ float b3tap(int t) {  // t in [-2, 2]
 
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
+// Zero-filling DPP lane moves inside a row of 16 lanes (old = 0, bound_ctrl): the form the compiler folds into a
+// following add or product (v_add_f32_dpp, v_mul_f32_dpp); it does not fold a lane move into a fused multiply-add.
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov0(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
 // Sum over the LPR (4, 8 or 16) consecutive lanes that own one image line, result in every lane.
-// xor-1 / xor-2 butterflies as quad permutes, then the half-row and row mirrors (DPP, no LDS).
+// xor-1 / xor-2 butterflies as quad permutes, then the half-row and row mirrors (DPP, no LDS): permutations inside a row,
+// so every source lane exists and a step is one v_add_f32_dpp.
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
-  const int iv = __builtin_bit_cast(int, v);
-  const int r = __builtin_amdgcn_update_dpp(iv, iv, CTRL, 0xF, 0xF, false);
-  return v + __builtin_bit_cast(float, r);
+  return v + dpp_mov0<CTRL>(v);
 }
 template <int LPR>
 __device__ __forceinline__ float line_sum(float v) {
@@ -91,8 +96,7 @@ __device__ __forceinline__ float line_sum(float v) {
 
 // Sum over the 64 lanes of the wave (valid in every lane): DPP butterflies inside each row of 16 lanes,
 // then the four row totals through scalar broadcasts.  All lanes must be active.
-__device__ __forceinline__ float wave_sum(float v) {
-  v = line_sum<16>(v);
+__device__ __forceinline__ float wave_rows_total(float v) {
   const int iv = __builtin_bit_cast(int, v);
   const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 0));
   const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 16));
@@ -100,12 +104,27 @@ __device__ __forceinline__ float wave_sum(float v) {
   const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 48));
   return (r0 + r1) + (r2 + r3);
 }
+__device__ __forceinline__ float wave_sum(float v) { return wave_rows_total(line_sum<16>(v)); }
+// Four wave sums stepped together: each is the chain of wave_sum (same additions, same order), and the wait states
+// between the dependent steps of one chain are filled by the other three.
+__device__ __forceinline__ void wave_sum4(float &a, float &b, float &c, float &d) {
+#define LC_STEP4(CTRL) \
+  a = dpp_add<CTRL>(a); \
+  b = dpp_add<CTRL>(b); \
+  c = dpp_add<CTRL>(c); \
+  d = dpp_add<CTRL>(d);
+  LC_STEP4(0xB1)
+  LC_STEP4(0x4E)
+  LC_STEP4(0x141)
+  LC_STEP4(0x140)
+#undef LC_STEP4
+  a = wave_rows_total(a);
+  b = wave_rows_total(b);
+  c = wave_rows_total(c);
+  d = wave_rows_total(d);
+}
 
 // Zero-filling DPP lane shifts inside one image line (LPR consecutive lanes, LPR | 16).
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov0(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 template <int K, int LPR>
 __device__ __forceinline__ float line_from_lower(float v, int lil) {  // value of lane - K of the same line, else 0
   if constexpr (K >= LPR) {
@@ -468,7 +487,8 @@ __device__ __forceinline__ void starlet_l1_grad_lds(const float img[PX], const f
 //   adjoint:  g[0] += b_1 sum_{x < D} y[x] + b_2 sum_{x < 2D} y[x],   g[N-1] likewise from the other end.
 // Neighbours in other lanes arrive by zero-filling DPP row shifts; a neighbour that lies in another line of the same
 // 16-lane DPP row is switched off through its tap coefficient (per lane, a handful of selects per pass) instead of a
-// select per fetched value, so that a tap is one multiply-add on a DPP operand.
+// select per fetched value, so that a tap is one multiply-add on a DPP operand (dpp_taps below: the compiler leaves a lane
+// move in front of a fused multiply-add, so the fused form is written out).
 struct LineLane {
   int lil;
   float is_first, is_last;  // 1 in the first / last lane of the line, else 0
@@ -483,22 +503,94 @@ __device__ __forceinline__ float swz_line_last(float v) {
   constexpr int pat = ((~(LPR - 1)) & 0x1F) | ((LPR - 1) << 5);
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), pat));
 }
-template <int K>
-__device__ __forceinline__ float dpp_lower(float v) {  // value of lane - K (same DPP row), 0 beyond the row
-  if constexpr (K >= 16) return 0.f; else return dpp_mov0<0x110 + K>(v);
+// The taps of one pass with the lane move riding on the multiply-add (v_fmac_f32_dpp acc, own, coef: acc += coef * own of
+// the lane K below / above, 0 beyond the DPP row) and the gated neighbours of the short dilations as v_mul_f32_dpp.  In
+// assembly, because the compiler does not fold a lane move into a fused multiply-add; one block per pass, tap-major, so that
+// consecutive instructions belong to different accumulators.  A block opens with the two wait states a DPP read needs after
+// a VALU write of its source (the compiler's hazard recogniser does not look inside), and nothing in a block reads through DPP
+// what the block wrote.
+#define LC_TAP1(a, o, c, dir, k) \
+  "v_fmac_f32_dpp %" #a ", %" #o ", %" #c " " dir ":%" #k " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define LC_TAP2(c, dir, k) LC_TAP1(0, 2, c, dir, k) LC_TAP1(1, 3, c, dir, k)
+#define LC_TAP4(c, dir, k) LC_TAP1(0, 4, c, dir, k) LC_TAP1(1, 5, c, dir, k) LC_TAP1(2, 6, c, dir, k) LC_TAP1(3, 7, c, dir, k)
+#define LC_TAP8(c, dir, k)                                                                                        \
+  LC_TAP1(0, 8, c, dir, k) LC_TAP1(1, 9, c, dir, k) LC_TAP1(2, 10, c, dir, k) LC_TAP1(3, 11, c, dir, k)             \
+  LC_TAP1(4, 12, c, dir, k) LC_TAP1(5, 13, c, dir, k) LC_TAP1(6, 14, c, dir, k) LC_TAP1(7, 15, c, dir, k)
+#define LC_MUL1(w, o, c, dir) "v_mul_f32_dpp %" #w ", %" #o ", %" #c " " dir ":1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+// per accumulator: lower K1, upper K1 (, lower K2, upper K2), the order of the multiply-adds they replace
+template <int K1, int K2>
+__device__ __forceinline__ void dpp_taps(float (&acc)[2], const float (&own)[2], float cl1, float cu1, float cl2, float cu2) {
+  asm("s_nop 1\n\t" LC_TAP2(4, "row_shr", 8) LC_TAP2(5, "row_shl", 8) LC_TAP2(6, "row_shr", 9) LC_TAP2(7, "row_shl", 9)
+      : "+v"(acc[0]), "+v"(acc[1])
+      : "v"(own[0]), "v"(own[1]), "v"(cl1), "v"(cu1), "v"(cl2), "v"(cu2), "n"(K1), "n"(K2));
 }
-template <int K>
-__device__ __forceinline__ float dpp_upper(float v) {  // value of lane + K (same DPP row), 0 beyond the row
-  if constexpr (K >= 16) return 0.f; else return dpp_mov0<0x100 + K>(v);
+template <int K1>
+__device__ __forceinline__ void dpp_taps(float (&acc)[2], const float (&own)[2], float cl1, float cu1) {
+  asm("s_nop 1\n\t" LC_TAP2(4, "row_shr", 6) LC_TAP2(5, "row_shl", 6)
+      : "+v"(acc[0]), "+v"(acc[1])
+      : "v"(own[0]), "v"(own[1]), "v"(cl1), "v"(cu1), "n"(K1));
 }
-template <int LPR>
-__device__ __forceinline__ float line_sum_fused(float v) {  // sum over the line's lanes, in every lane
-  v += dpp_mov0<0xB1>(v);                             // quad_perm [1,0,3,2]
-  v += dpp_mov0<0x4E>(v);                             // quad_perm [2,3,0,1]
-  if constexpr (LPR >= 8) v += dpp_mov0<0x141>(v);    // row_half_mirror
-  if constexpr (LPR >= 16) v += dpp_mov0<0x140>(v);   // row_mirror
-  return v;
+template <int K1, int K2>
+__device__ __forceinline__ void dpp_taps(float (&acc)[4], const float (&own)[4], float cl1, float cu1, float cl2, float cu2) {
+  asm("s_nop 1\n\t" LC_TAP4(8, "row_shr", 12) LC_TAP4(9, "row_shl", 12) LC_TAP4(10, "row_shr", 13) LC_TAP4(11, "row_shl", 13)
+      : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])
+      : "v"(own[0]), "v"(own[1]), "v"(own[2]), "v"(own[3]), "v"(cl1), "v"(cu1), "v"(cl2), "v"(cu2), "n"(K1), "n"(K2));
 }
+template <int K1>
+__device__ __forceinline__ void dpp_taps(float (&acc)[4], const float (&own)[4], float cl1, float cu1) {
+  asm("s_nop 1\n\t" LC_TAP4(8, "row_shr", 10) LC_TAP4(9, "row_shl", 10)
+      : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3])
+      : "v"(own[0]), "v"(own[1]), "v"(own[2]), "v"(own[3]), "v"(cl1), "v"(cu1), "n"(K1));
+}
+template <int K1, int K2>
+__device__ __forceinline__ void dpp_taps(float (&acc)[8], const float (&own)[8], float cl1, float cu1, float cl2, float cu2) {
+  asm("s_nop 1\n\t" LC_TAP8(16, "row_shr", 20) LC_TAP8(17, "row_shl", 20) LC_TAP8(18, "row_shr", 21) LC_TAP8(19, "row_shl", 21)
+      : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7])
+      : "v"(own[0]), "v"(own[1]), "v"(own[2]), "v"(own[3]), "v"(own[4]), "v"(own[5]), "v"(own[6]), "v"(own[7]), "v"(cl1),
+        "v"(cu1), "v"(cl2), "v"(cu2), "n"(K1), "n"(K2));
+}
+template <int K1>
+__device__ __forceinline__ void dpp_taps(float (&acc)[8], const float (&own)[8], float cl1, float cu1) {
+  asm("s_nop 1\n\t" LC_TAP8(16, "row_shr", 18) LC_TAP8(17, "row_shl", 18)
+      : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7])
+      : "v"(own[0]), "v"(own[1]), "v"(own[2]), "v"(own[3]), "v"(own[4]), "v"(own[5]), "v"(own[6]), "v"(own[7]), "v"(cl1),
+        "v"(cu1), "n"(K1));
+}
+// w[i] = gate * (in[i] of the adjacent lower (SHR) or upper lane, 0 beyond the DPP row), M = 2, 4 or 8 values
+template <bool SHR>
+__device__ __forceinline__ void dpp_gated(float *w, const float *in, float gate, std::integral_constant<int, 2>) {
+  if constexpr (SHR)
+    asm("s_nop 1\n\t" LC_MUL1(0, 2, 4, "row_shr") LC_MUL1(1, 3, 4, "row_shr") : "=&v"(w[0]), "=&v"(w[1]) : "v"(in[0]), "v"(in[1]), "v"(gate));
+  else
+    asm("s_nop 1\n\t" LC_MUL1(0, 2, 4, "row_shl") LC_MUL1(1, 3, 4, "row_shl") : "=&v"(w[0]), "=&v"(w[1]) : "v"(in[0]), "v"(in[1]), "v"(gate));
+}
+#define LC_MUL4(dir) LC_MUL1(0, 4, 8, dir) LC_MUL1(1, 5, 8, dir) LC_MUL1(2, 6, 8, dir) LC_MUL1(3, 7, 8, dir)
+template <bool SHR>
+__device__ __forceinline__ void dpp_gated(float *w, const float *in, float gate, std::integral_constant<int, 4>) {
+  if constexpr (SHR)
+    asm("s_nop 1\n\t" LC_MUL4("row_shr") : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3]) : "v"(in[0]), "v"(in[1]), "v"(in[2]), "v"(in[3]), "v"(gate));
+  else
+    asm("s_nop 1\n\t" LC_MUL4("row_shl") : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3]) : "v"(in[0]), "v"(in[1]), "v"(in[2]), "v"(in[3]), "v"(gate));
+}
+#undef LC_MUL4
+#define LC_MUL8(dir)                                                                                \
+  LC_MUL1(0, 8, 16, dir) LC_MUL1(1, 9, 16, dir) LC_MUL1(2, 10, 16, dir) LC_MUL1(3, 11, 16, dir)       \
+  LC_MUL1(4, 12, 16, dir) LC_MUL1(5, 13, 16, dir) LC_MUL1(6, 14, 16, dir) LC_MUL1(7, 15, 16, dir)
+#define LC_MUL8_OPS                                                                                                      \
+  : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3]), "=&v"(w[4]), "=&v"(w[5]), "=&v"(w[6]), "=&v"(w[7])                 \
+  : "v"(in[0]), "v"(in[1]), "v"(in[2]), "v"(in[3]), "v"(in[4]), "v"(in[5]), "v"(in[6]), "v"(in[7]), "v"(gate)
+template <bool SHR>
+__device__ __forceinline__ void dpp_gated(float *w, const float *in, float gate, std::integral_constant<int, 8>) {
+  if constexpr (SHR) asm("s_nop 1\n\t" LC_MUL8("row_shr") LC_MUL8_OPS);
+  else asm("s_nop 1\n\t" LC_MUL8("row_shl") LC_MUL8_OPS);
+}
+#undef LC_MUL8_OPS
+#undef LC_MUL8
+#undef LC_MUL1
+#undef LC_TAP8
+#undef LC_TAP4
+#undef LC_TAP2
+#undef LC_TAP1
 
 template <int N, int PX, int LPR, int D, bool ADJ>
 __device__ __forceinline__ void line_pass(const float (&own)[PX], const LineLane &L, float (&out)[PX]) {
@@ -515,23 +607,14 @@ __device__ __forceinline__ void line_pass(const float (&own)[PX], const LineLane
     float e = 0.f;
     if constexpr (!ADJ) e = fmaf(ef, swz_line_first<LPR>(own[0]), el * swz_line_last<LPR>(own[PX - 1]));
 #pragma unroll
-    for (int p = 0; p < PX; ++p) {
-      float acc = fmaf(b0, own[p], e);
-      if constexpr (K1 < LPR) {
-        acc = fmaf(cl1, dpp_lower<K1>(own[p]), acc);
-        acc = fmaf(cu1, dpp_upper<K1>(own[p]), acc);
-      }
-      if constexpr (K2 < LPR) {
-        acc = fmaf(cl2, dpp_lower<K2>(own[p]), acc);
-        acc = fmaf(cu2, dpp_upper<K2>(own[p]), acc);
-      }
-      out[p] = acc;
-    }
+    for (int p = 0; p < PX; ++p) out[p] = fmaf(b0, own[p], e);
+    if constexpr (K2 < LPR) dpp_taps<K1, K2>(out, own, cl1, cu1, cl2, cu2);
+    else if constexpr (K1 < LPR) dpp_taps<K1>(out, own, cl1, cu1);
     if constexpr (ADJ) {
       float full = own[0];
 #pragma unroll
       for (int p = 1; p < PX; ++p) full += own[p];
-      const float hs = line_sum_fused<LPR>(full * ef), ts = line_sum_fused<LPR>(full * el);
+      const float hs = line_sum<LPR>(full * ef), ts = line_sum<LPR>(full * el);
       out[0] = fmaf(L.is_first, hs, out[0]);
       out[PX - 1] = fmaf(L.is_last, ts, out[PX - 1]);
     }
@@ -541,10 +624,12 @@ __device__ __forceinline__ void line_pass(const float (&own)[PX], const LineLane
     float w[3 * PX];  // [lower lane | own | upper lane], only the entries the stencil touches are formed
 #pragma unroll
     for (int q = 0; q < PX; ++q) {
-      w[q] = (q >= PX - 2 * D) ? has_lower * dpp_lower<1>(own[q]) : 0.f;
+      w[q] = 0.f;
       w[PX + q] = own[q];
-      w[2 * PX + q] = (q < 2 * D) ? has_upper * dpp_upper<1>(own[q]) : 0.f;
+      w[2 * PX + q] = 0.f;
     }
+    dpp_gated<true>(&w[PX - 2 * D], &own[PX - 2 * D], has_lower, std::integral_constant<int, 2 * D>{});  // the last 2 D of the lower lane
+    dpp_gated<false>(&w[2 * PX], &own[0], has_upper, std::integral_constant<int, 2 * D>{});             // the first 2 D of the upper lane
 #pragma unroll
     for (int p = 0; p < PX; ++p) {
       float acc = b0 * own[p];

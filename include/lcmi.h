@@ -100,6 +100,40 @@ int lc_detect_cosmics(lc_ctx *ctx, int K, int n, const float *data, const float 
                       const uint8_t *inmask /*nullable*/, const lc_cosmics_cfg *cfg, uint8_t *crmask,
                       float *clean /*nullable*/, int32_t *iters /*nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- bad rows and columns of the stamps: replaces ccdproc.ccdmask inside mask_cutout ------------
+ * Reference call site: lightcurver/processes/cutout_making.py:67-80 (once per stamp, when mask_bad_rows_and_columns is
+ * set, config.yaml:208): ccdmask(ccd, findbadcolumns=True), then the columns and rows flagged at both ends of the stamp.
+ * ccdmask(byblocks=False) as frozen in DESIGN.md section 5 "Bad rows and columns": R = D - med7x7(D) (scipy's reflect
+ * boundary), sigma = (P(69.1) - P(30.9)) / 2 of R (NumPy's linear percentile, in float32), flagged where R < -lsigma sigma
+ * or R > hsigma sigma or D is not finite (sigma = NaN for a stamp with such a pixel: nothing else is flagged there), gaps
+ * of at most ngood pixels between flagged pixels of a column filled (findbadcolumns).
+ *   data [K][n][n].  Outputs, any may be NULL but not all: mask [K][n][n] the ccdmask result (1 = bad); bad_cols [K][n],
+ *   bad_rows [K][n]: mask set at both ends of the column / row; rowcol [K][n][n]: those columns and rows, whole (what
+ *   mask_cutout ORs into the cosmics mask); sigma [K]; kernel_ms = device time of the kernel (HIP events).
+ * Any square n from 8 to 128 (lc_ccdmask_supported, no device needed; LC_ERR_UNSUPPORTED otherwise), any K, one launch.
+ * LC_ERR_UNSUPPORTED: byblocks != 0, ncmed or nlmed != 7.  LC_ERR_INVALID: lsigma or hsigma not finite, ngood < 0. */
+typedef struct {
+  int32_t ncmed, nlmed;   /* 7, 7 (the only window built) */
+  float lsigma, hsigma;   /* 9.0, 9.0 */
+  int32_t ngood;          /* 5 */
+  int32_t byblocks;       /* 0 (the only one built) */
+  int32_t findbadcolumns; /* 1: fill the short gaps along columns; 0: the mask of the threshold alone */
+} lc_ccdmask_cfg;
+int lc_ccdmask_supported(int n);
+int lc_ccdmask_stamps(lc_ctx *ctx, int K, int n, const float *data, const lc_ccdmask_cfg *cfg, uint8_t *mask /*nullable*/,
+                      uint8_t *rowcol /*nullable*/, uint8_t *bad_cols /*nullable*/, uint8_t *bad_rows /*nullable*/,
+                      float *sigma /*nullable*/, float *kernel_ms /*nullable*/);
+
+/* ---- the whole of the reference's mask_cutout (cutout_making.py:54-91) in one call ------------
+ * The stack is uploaded once; with do_bad_columns the rowcol of lc_ccdmask_stamps, with do_cosmics the crmask of
+ * lc_detect_cosmics(invar = noisemap^2, formed on the device, no inmask), ORed on the device: mask [K][n][n], 1 = masked.
+ * noisemap and cosmics_cfg may be NULL without do_cosmics, ccdmask_cfg without do_bad_columns; both switches off gives
+ * a zero mask without a device call.  Sizes and error codes are those of the two calls; kernel_ms = device time of all
+ * kernels (HIP events). */
+int lc_mask_cutouts(lc_ctx *ctx, int K, int n, const float *data, const float *noisemap /*nullable*/, int do_bad_columns,
+                    int do_cosmics, const lc_cosmics_cfg *cosmics_cfg /*nullable*/,
+                    const lc_ccdmask_cfg *ccdmask_cfg /*nullable*/, uint8_t *mask, float *kernel_ms /*nullable*/);
+
 /* ---- neighbouring sources of the star stamps: replaces sep.extract inside mask_surrounding_stars -----------
  * Reference call site: lightcurver/processes/psf_modelling.py:45 (once per star stamp, loop at :129-133) with
  * thresh = 3, minarea = 15, deblend_cont = 0.001 and sep's defaults deblend_nthresh = 32, clean = True, clean_param = 1.

@@ -46,6 +46,11 @@ class CosmicsCfg(C.Structure):
                 ('cleantype', C.c_int32), ('fsmode', C.c_int32)]
 
 
+class CcdmaskCfg(C.Structure):
+    _fields_ = [('ncmed', C.c_int32), ('nlmed', C.c_int32), ('lsigma', C.c_float), ('hsigma', C.c_float),
+                ('ngood', C.c_int32), ('byblocks', C.c_int32), ('findbadcolumns', C.c_int32)]
+
+
 class SegmentCfg(C.Structure):
     _fields_ = [('thresh', C.c_float), ('minarea', C.c_int32), ('deblend_nthresh', C.c_int32),
                 ('deblend_cont', C.c_float), ('clean_param', C.c_float), ('clean', C.c_int32)]
@@ -70,6 +75,12 @@ SIGNATURES = {
     'lc_cosmics_supported': (C.c_int, [C.c_int]),
     'lc_detect_cosmics': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_uint8), C.POINTER(CosmicsCfg),
                                     C.POINTER(C.c_uint8), fp, ip, C.POINTER(C.c_float)]),
+    'lc_ccdmask_supported': (C.c_int, [C.c_int]),
+    'lc_ccdmask_stamps': (C.c_int, [vp, C.c_int, C.c_int, fp, C.POINTER(CcdmaskCfg), C.POINTER(C.c_uint8),
+                                    C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), fp,
+                                    C.POINTER(C.c_float)]),
+    'lc_mask_cutouts': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.POINTER(CosmicsCfg),
+                                  C.POINTER(CcdmaskCfg), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     'lc_segment_supported': (C.c_int, [C.c_int]),
     'lc_segment_stamps': (C.c_int, [vp, C.c_int, C.c_int, fp, fp, C.POINTER(SegmentCfg), C.POINTER(C.c_uint8), ip, ip, fp,
                                     ip, C.POINTER(C.c_float)]),

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cosmics_device.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -278,6 +279,64 @@ __global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
   }
 }
 
+int cosmics_check(lc_ctx *ctx, const char *who, int n, const lc_cosmics_cfg *cfg) {
+  const std::string w(who);
+  if (n < kCrMinN || n > kCrMaxN) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, w + ": stamp size outside 8 .. 128");
+  if (cfg->cleantype != 0 || cfg->fsmode != 0)
+    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, w + ": only cleantype = meanmask and fsmode = median are built");
+  if (!(cfg->gain > 0.f) || !std::isfinite(cfg->gain) || !std::isfinite(cfg->readnoise) ||
+      !std::isfinite(cfg->sigclip) || !std::isfinite(cfg->sigfrac) || !std::isfinite(cfg->objlim) ||
+      std::isnan(cfg->satlevel) || cfg->niter < 0)
+    LC_FAIL(ctx, LC_ERR_INVALID, w + ": invalid settings");
+  return LC_OK;
+}
+
+static int cosmics_grid(const lc_ctx *ctx, int K, int n) {
+  return n <= kCrLdsMaxN ? K : std::min(K, std::max(ctx->n_cu, 1) * 2);
+}
+
+size_t cosmics_scratch_bytes(const lc_ctx *ctx, int K, int n) {
+  return n <= kCrLdsMaxN ? 0 : (size_t)cosmics_grid(ctx, K, n) * cr_plane_bytes(n);
+}
+
+hipError_t cosmics_launch(lc_ctx *ctx, int K, int n, const float *data, const float *invar, const uint8_t *inmask,
+                          const lc_cosmics_cfg *cfg, uint8_t *crmask, float *clean, int32_t *iters, float *scratch) {
+  CrArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.K = K;
+  A.n = n;
+  A.niter = cfg->niter;
+  A.sepmed = cfg->sepmed != 0;
+  A.have_invar = invar != nullptr;
+  A.data = data;
+  A.invar = invar;
+  A.inmask = inmask;
+  A.crmask = crmask;
+  A.clean = clean;
+  A.iters = iters;
+  A.scratch = scratch;
+  A.gain = cfg->gain;
+  A.gain2 = cfg->gain * cfg->gain;
+  A.rn2 = cfg->readnoise * cfg->readnoise;
+  A.vhole = 1e-5f + A.rn2;
+  A.satg = cfg->gain * cfg->satlevel;
+  A.satg10 = A.satg / 10.0f;
+  A.sigclip = cfg->sigclip;
+  A.sigcliplow = cfg->sigfrac * cfg->sigclip;
+  A.objlim = cfg->objlim;
+  const int grid = cosmics_grid(ctx, K, n);
+  if (n <= kCrLdsMaxN) {
+    const size_t lds_bytes = cr_plane_bytes(n);
+    hipError_t e = hipFuncSetAttribute((const void *)cosmics_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cosmics_kernel<true>, dim3(grid), dim3(kCrThreads), lds_bytes, ctx->stream, A);
+  } else {
+    hipLaunchKernelGGL(cosmics_kernel<false>, dim3(grid), dim3(kCrThreads), 0, ctx->stream, A);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace lc
 
 using namespace lc;
@@ -290,18 +349,9 @@ int lc_detect_cosmics(lc_ctx *ctx, int K, int n, const float *data, const float 
                       const lc_cosmics_cfg *cfg, uint8_t *crmask, float *clean, int32_t *iters, float *kernel_ms) {
   if (!ctx) return LC_ERR_INVALID;
   if (K <= 0 || !data || !cfg || !crmask) LC_FAIL(ctx, LC_ERR_INVALID, "lc_detect_cosmics: invalid argument");
-  if (!lc_cosmics_supported(n))
-    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_detect_cosmics: stamp size outside 8 .. 128");
-  if (cfg->cleantype != 0 || cfg->fsmode != 0)
-    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_detect_cosmics: only cleantype = meanmask and fsmode = median are built");
-  if (!(cfg->gain > 0.f) || !std::isfinite(cfg->gain) || !std::isfinite(cfg->readnoise) ||
-      !std::isfinite(cfg->sigclip) || !std::isfinite(cfg->sigfrac) || !std::isfinite(cfg->objlim) ||
-      std::isnan(cfg->satlevel) || cfg->niter < 0)
-    LC_FAIL(ctx, LC_ERR_INVALID, "lc_detect_cosmics: invalid settings");
+  if (int rc = cosmics_check(ctx, "lc_detect_cosmics", n, cfg)) return rc;
   LC_ENTER(ctx);
   const size_t np = (size_t)n * n, tot = (size_t)K * np;
-  const bool lds = n <= kCrLdsMaxN;
-  const int grid = lds ? K : std::min(K, std::max(ctx->n_cu, 1) * 2);
   std::vector<void *> dev;
   auto cleanup = [&]() {
     for (void *p : dev) (void)hipFree(p);
@@ -320,65 +370,29 @@ int lc_detect_cosmics(lc_ctx *ctx, int K, int n, const float *data, const float 
       return LC_ERR_DEVICE;                                       \
     }                                                             \
   } while (0)
-  CrArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.K = K;
-  A.n = n;
-  A.niter = cfg->niter;
-  A.sepmed = cfg->sepmed != 0;
-  A.have_invar = invar != nullptr;
-  A.gain = cfg->gain;
-  A.gain2 = cfg->gain * cfg->gain;
-  A.rn2 = cfg->readnoise * cfg->readnoise;
-  A.vhole = 1e-5f + A.rn2;
-  A.satg = cfg->gain * cfg->satlevel;
-  A.satg10 = A.satg / 10.0f;
-  A.sigclip = cfg->sigclip;
-  A.sigcliplow = cfg->sigfrac * cfg->sigclip;
-  A.objlim = cfg->objlim;
-  void *p = nullptr;
-  CR_TRY(alloc(tot * 4, &p));
-  A.data = (const float *)p;
-  CR_TRY(hipMemcpyAsync(p, data, tot * 4, hipMemcpyHostToDevice, ctx->stream));
+  float *d_data = nullptr, *d_invar = nullptr, *d_clean = nullptr, *d_scratch = nullptr;
+  uint8_t *d_inmask = nullptr, *d_crmask = nullptr;
+  int32_t *d_iters = nullptr;
+  CR_TRY(alloc(tot * 4, (void **)&d_data));
+  CR_TRY(hipMemcpyAsync(d_data, data, tot * 4, hipMemcpyHostToDevice, ctx->stream));
   if (invar) {
-    CR_TRY(alloc(tot * 4, &p));
-    A.invar = (const float *)p;
-    CR_TRY(hipMemcpyAsync(p, invar, tot * 4, hipMemcpyHostToDevice, ctx->stream));
+    CR_TRY(alloc(tot * 4, (void **)&d_invar));
+    CR_TRY(hipMemcpyAsync(d_invar, invar, tot * 4, hipMemcpyHostToDevice, ctx->stream));
   }
   if (inmask) {
-    CR_TRY(alloc(tot, &p));
-    A.inmask = (const uint8_t *)p;
-    CR_TRY(hipMemcpyAsync(p, inmask, tot, hipMemcpyHostToDevice, ctx->stream));
+    CR_TRY(alloc(tot, (void **)&d_inmask));
+    CR_TRY(hipMemcpyAsync(d_inmask, inmask, tot, hipMemcpyHostToDevice, ctx->stream));
   }
-  CR_TRY(alloc(tot, &p));
-  A.crmask = (uint8_t *)p;
-  if (clean) {
-    CR_TRY(alloc(tot * 4, &p));
-    A.clean = (float *)p;
-  }
-  if (iters) {
-    CR_TRY(alloc((size_t)K * 4, &p));
-    A.iters = (int *)p;
-  }
-  size_t lds_bytes = 0;
-  if (lds) {
-    lds_bytes = cr_plane_bytes(n);
-    CR_TRY(hipFuncSetAttribute((const void *)cosmics_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds_bytes));
-  } else {
-    CR_TRY(alloc((size_t)grid * cr_plane_bytes(n), &p));
-    A.scratch = (float *)p;
-  }
+  CR_TRY(alloc(tot, (void **)&d_crmask));
+  if (clean) CR_TRY(alloc(tot * 4, (void **)&d_clean));
+  if (iters) CR_TRY(alloc((size_t)K * 4, (void **)&d_iters));
+  if (const size_t sb = cosmics_scratch_bytes(ctx, K, n)) CR_TRY(alloc(sb, (void **)&d_scratch));
   CR_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-  if (lds)
-    hipLaunchKernelGGL(cosmics_kernel<true>, dim3(grid), dim3(kCrThreads), lds_bytes, ctx->stream, A);
-  else
-    hipLaunchKernelGGL(cosmics_kernel<false>, dim3(grid), dim3(kCrThreads), 0, ctx->stream, A);
-  CR_TRY(hipGetLastError());
+  CR_TRY(cosmics_launch(ctx, K, n, d_data, d_invar, d_inmask, cfg, d_crmask, d_clean, d_iters, d_scratch));
   CR_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  CR_TRY(hipMemcpyAsync(crmask, A.crmask, tot, hipMemcpyDeviceToHost, ctx->stream));
-  if (clean) CR_TRY(hipMemcpyAsync(clean, A.clean, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (iters) CR_TRY(hipMemcpyAsync(iters, A.iters, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
+  CR_TRY(hipMemcpyAsync(crmask, d_crmask, tot, hipMemcpyDeviceToHost, ctx->stream));
+  if (clean) CR_TRY(hipMemcpyAsync(clean, d_clean, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (iters) CR_TRY(hipMemcpyAsync(iters, d_iters, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
   CR_TRY(hipStreamSynchronize(ctx->stream));
   if (kernel_ms) CR_TRY(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
   cleanup();

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <vector>
 
+#include "device_call.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -280,44 +281,25 @@ int lc_align_stack(lc_ctx *ctx, int C, int E, int n, const float *cubes, const f
   }
   LC_ENTER(ctx);
   const size_t np = (size_t)n * n, tot = (size_t)C * E * np;
-  std::vector<void *> dev;
-  auto cleanup = [&]() {
-    for (void *p : dev) (void)hipFree(p);
-  };
-  auto alloc = [&](size_t bytes, void **d) -> hipError_t {
-    hipError_t e = hipMalloc(d, bytes);
-    if (e == hipSuccess) dev.push_back(*d);
-    return e;
-  };
-#define AL_TRY(call)                                              \
-  do {                                                            \
-    hipError_t e_ = (call);                                       \
-    if (e_ != hipSuccess) {                                       \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-      cleanup();                                                  \
-      return LC_ERR_DEVICE;                                       \
-    }                                                             \
-  } while (0)
-  void *d_in = nullptr, *d_al = nullptr, *d_geo = nullptr, *d_noise = nullptr, *d_stack = nullptr, *d_med = nullptr,
-       *d_rej = nullptr;
-  AL_TRY(alloc(tot * 4, &d_in));
-  AL_TRY(hipMemcpyAsync(d_in, cubes, tot * 4, hipMemcpyHostToDevice, ctx->stream));
+  DeviceCall call(ctx);
+  const float *d_in = nullptr, *d_noise = nullptr;
+  const double *d_geo = nullptr;
+  float *d_al = nullptr, *d_stack = nullptr, *d_med = nullptr;
+  int32_t *d_rej = nullptr;
+  LC_HIP(ctx, call.upload(cubes, tot, &d_in));
   if (align) {
-    AL_TRY(alloc(tot * 4, &d_al));
-    AL_TRY(alloc(geo.size() * sizeof(double), &d_geo));
-    AL_TRY(hipMemcpyAsync(d_geo, geo.data(), geo.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    LC_HIP(ctx, call.alloc(tot, &d_al));
+    LC_HIP(ctx, call.upload(geo.data(), geo.size(), &d_geo));
   }
-  if (weighted) {
-    AL_TRY(alloc((size_t)E * np * 4, &d_noise));
-    AL_TRY(hipMemcpyAsync(d_noise, noisemap, (size_t)E * np * 4, hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (stack) AL_TRY(alloc((size_t)C * np * 4, &d_stack));
-  if (median) AL_TRY(alloc((size_t)C * np * 4, &d_med));
-  if (n_rejected) AL_TRY(alloc((size_t)C * np * 4, &d_rej));
+  if (weighted) LC_HIP(ctx, call.upload(noisemap, (size_t)E * np, &d_noise));
+  LC_HIP(ctx, call.result(stack, (size_t)C * np, &d_stack));
+  LC_HIP(ctx, call.result(median, (size_t)C * np, &d_med));
+  LC_HIP(ctx, call.result(n_rejected, (size_t)C * np, &d_rej));
   const size_t lds_bytes = al_lds_bytes(n);
   if (align)
-    AL_TRY(hipFuncSetAttribute((const void *)align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  AL_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    LC_HIP(ctx, hipFuncSetAttribute((const void *)align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes));
+  LC_HIP(ctx, call.start());
   if (align) {
     const double zd = std::sqrt(3.0) - 2.0;
     AlignArgs A;
@@ -326,38 +308,33 @@ int lc_align_stack(lc_ctx *ctx, int C, int E, int n, const float *cubes, const f
     A.gain = 6.0f;
     A.den = (float)(1.0 - std::pow(zd, (double)(2 * n - 2)));
     A.last = (float)(zd / (zd * zd - 1.0));
-    A.in = (const float *)d_in;
-    A.out = (float *)d_al;
-    A.geo = (const double *)d_geo;
+    A.in = d_in;
+    A.out = d_al;
+    A.geo = d_geo;
     A.E = E;
     hipLaunchKernelGGL(align_kernel, dim3((unsigned)((size_t)C * E)), dim3(kAlThreads), lds_bytes, ctx->stream, A);
-    AL_TRY(hipGetLastError());
+    LC_HIP(ctx, hipGetLastError());
   }
-  const void *d_val = align ? d_al : d_in;
+  const float *d_val = align ? d_al : d_in;
   if (stacked) {
     StackArgs S;
     S.E = E;
     S.np = (int)np;
     S.clip = cf.clip != 0;
     S.n_sigma = cf.n_sigma;
-    S.v = (const float *)d_val;
-    S.noise = (const float *)d_noise;
-    S.stack = (float *)d_stack;
-    S.median = (float *)d_med;
-    S.nrej = (int32_t *)d_rej;
+    S.v = d_val;
+    S.noise = d_noise;
+    S.stack = d_stack;
+    S.median = d_med;
+    S.nrej = d_rej;
     hipLaunchKernelGGL(stack_kernel, dim3((unsigned)((np + kStThreads - 1) / kStThreads), (unsigned)C), dim3(kStThreads),
                        0, ctx->stream, S);
-    AL_TRY(hipGetLastError());
+    LC_HIP(ctx, hipGetLastError());
   }
-  AL_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  if (aligned) AL_TRY(hipMemcpyAsync(aligned, d_val, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (stack) AL_TRY(hipMemcpyAsync(stack, d_stack, (size_t)C * np * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (median) AL_TRY(hipMemcpyAsync(median, d_med, (size_t)C * np * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (n_rejected) AL_TRY(hipMemcpyAsync(n_rejected, d_rej, (size_t)C * np * 4, hipMemcpyDeviceToHost, ctx->stream));
-  AL_TRY(hipStreamSynchronize(ctx->stream));
-  if (kernel_ms) AL_TRY(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
-  cleanup();
-#undef AL_TRY
+  LC_HIP(ctx, call.stop());
+  // the aligned cubes are the align kernel's work space (or, without alignment, the input): not a result() buffer
+  if (aligned) LC_HIP(ctx, hipMemcpyAsync(aligned, d_val, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
+  LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;
 }
 

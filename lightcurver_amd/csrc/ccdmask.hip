@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cosmics_device.h"
+#include "device_call.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -286,20 +287,6 @@ static hipError_t ccdmask_launch(lc_ctx *ctx, int K, int n, const float *data, c
   return hipGetLastError();
 }
 
-// device buffers of one call, freed when it returns
-struct DevPool {
-  std::vector<void *> held;
-  ~DevPool() {
-    for (void *p : held) (void)hipFree(p);
-  }
-  template <class T>
-  hipError_t alloc(size_t count, T **d) {
-    hipError_t e = hipMalloc((void **)d, count * sizeof(T));
-    if (e == hipSuccess) held.push_back(*d);
-    return e;
-  }
-};
-
 }  // namespace lc
 
 using namespace lc;
@@ -316,26 +303,20 @@ int lc_ccdmask_stamps(lc_ctx *ctx, int K, int n, const float *data, const lc_ccd
   if (int rc = ccdmask_check(ctx, "lc_ccdmask_stamps", n, cfg)) return rc;
   LC_ENTER(ctx);
   const size_t np = (size_t)n * n, tot = (size_t)K * np, lines = (size_t)K * n;
-  DevPool pool;
-  float *d_data = nullptr, *d_sigma = nullptr;
+  DeviceCall call(ctx);
+  const float *d_data = nullptr;
+  float *d_sigma = nullptr;
   uint8_t *d_mask = nullptr, *d_rowcol = nullptr, *d_cols = nullptr, *d_rows = nullptr;
-  LC_HIP(ctx, pool.alloc(tot, &d_data));
-  LC_HIP(ctx, hipMemcpyAsync(d_data, data, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (mask) LC_HIP(ctx, pool.alloc(tot, &d_mask));
-  if (rowcol) LC_HIP(ctx, pool.alloc(tot, &d_rowcol));
-  if (bad_cols) LC_HIP(ctx, pool.alloc(lines, &d_cols));
-  if (bad_rows) LC_HIP(ctx, pool.alloc(lines, &d_rows));
-  if (sigma) LC_HIP(ctx, pool.alloc((size_t)K, &d_sigma));
-  LC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  LC_HIP(ctx, call.upload(data, tot, &d_data));
+  LC_HIP(ctx, call.result(mask, tot, &d_mask));
+  LC_HIP(ctx, call.result(rowcol, tot, &d_rowcol));
+  LC_HIP(ctx, call.result(bad_cols, lines, &d_cols));
+  LC_HIP(ctx, call.result(bad_rows, lines, &d_rows));
+  LC_HIP(ctx, call.result(sigma, (size_t)K, &d_sigma));
+  LC_HIP(ctx, call.start());
   LC_HIP(ctx, ccdmask_launch(ctx, K, n, d_data, cfg, d_mask, d_rowcol, d_cols, d_rows, d_sigma));
-  LC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  if (mask) LC_HIP(ctx, hipMemcpyAsync(mask, d_mask, tot, hipMemcpyDeviceToHost, ctx->stream));
-  if (rowcol) LC_HIP(ctx, hipMemcpyAsync(rowcol, d_rowcol, tot, hipMemcpyDeviceToHost, ctx->stream));
-  if (bad_cols) LC_HIP(ctx, hipMemcpyAsync(bad_cols, d_cols, lines, hipMemcpyDeviceToHost, ctx->stream));
-  if (bad_rows) LC_HIP(ctx, hipMemcpyAsync(bad_rows, d_rows, lines, hipMemcpyDeviceToHost, ctx->stream));
-  if (sigma) LC_HIP(ctx, hipMemcpyAsync(sigma, d_sigma, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
-  LC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (kernel_ms) LC_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+  LC_HIP(ctx, call.stop());
+  LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;
 }
 
@@ -356,20 +337,20 @@ int lc_mask_cutouts(lc_ctx *ctx, int K, int n, const float *data, const float *n
     return LC_OK;
   }
   LC_ENTER(ctx);
-  DevPool pool;
-  float *d_data = nullptr, *d_invar = nullptr, *d_scratch = nullptr;
+  DeviceCall call(ctx);
+  const float *d_data = nullptr;
+  float *d_invar = nullptr, *d_scratch = nullptr;
   uint8_t *d_mask = nullptr, *d_lines = nullptr;
-  LC_HIP(ctx, pool.alloc(tot, &d_data));
-  LC_HIP(ctx, hipMemcpyAsync(d_data, data, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-  LC_HIP(ctx, pool.alloc(tot, &d_mask));
+  LC_HIP(ctx, call.upload(data, tot, &d_data));
+  LC_HIP(ctx, call.result(mask, tot, &d_mask));
   if (do_cosmics) {
-    LC_HIP(ctx, pool.alloc(tot, &d_invar));
+    LC_HIP(ctx, call.alloc(tot, &d_invar));  // the noise map, squared in place: not upload()'s read-only input
     LC_HIP(ctx, hipMemcpyAsync(d_invar, noisemap, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (const size_t sb = cosmics_scratch_bytes(ctx, K, n)) LC_HIP(ctx, pool.alloc(sb / 4, &d_scratch));
-    if (do_bad_columns) LC_HIP(ctx, pool.alloc(tot, &d_lines));
+    if (const size_t sb = cosmics_scratch_bytes(ctx, K, n)) LC_HIP(ctx, call.alloc(sb / 4, &d_scratch));
+    if (do_bad_columns) LC_HIP(ctx, call.alloc(tot, &d_lines));
   }
   const unsigned blocks = (unsigned)((tot + 255) / 256);
-  LC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  LC_HIP(ctx, call.start());
   if (do_cosmics) {
     hipLaunchKernelGGL(square_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_invar, d_invar, tot);
     LC_HIP(ctx, hipGetLastError());
@@ -383,10 +364,8 @@ int lc_mask_cutouts(lc_ctx *ctx, int K, int n, const float *data, const float *n
       LC_HIP(ctx, hipGetLastError());
     }
   }
-  LC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  LC_HIP(ctx, hipMemcpyAsync(mask, d_mask, tot, hipMemcpyDeviceToHost, ctx->stream));
-  LC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (kernel_ms) LC_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+  LC_HIP(ctx, call.stop());
+  LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;
 }
 

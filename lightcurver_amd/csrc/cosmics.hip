@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cosmics_device.h"
+#include "device_call.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -352,51 +353,23 @@ int lc_detect_cosmics(lc_ctx *ctx, int K, int n, const float *data, const float 
   if (int rc = cosmics_check(ctx, "lc_detect_cosmics", n, cfg)) return rc;
   LC_ENTER(ctx);
   const size_t np = (size_t)n * n, tot = (size_t)K * np;
-  std::vector<void *> dev;
-  auto cleanup = [&]() {
-    for (void *p : dev) (void)hipFree(p);
-  };
-  auto alloc = [&](size_t bytes, void **d) -> hipError_t {
-    hipError_t e = hipMalloc(d, bytes);
-    if (e == hipSuccess) dev.push_back(*d);
-    return e;
-  };
-#define CR_TRY(call)                                              \
-  do {                                                            \
-    hipError_t e_ = (call);                                       \
-    if (e_ != hipSuccess) {                                       \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-      cleanup();                                                  \
-      return LC_ERR_DEVICE;                                       \
-    }                                                             \
-  } while (0)
-  float *d_data = nullptr, *d_invar = nullptr, *d_clean = nullptr, *d_scratch = nullptr;
-  uint8_t *d_inmask = nullptr, *d_crmask = nullptr;
+  DeviceCall call(ctx);
+  const float *d_data = nullptr, *d_invar = nullptr;
+  const uint8_t *d_inmask = nullptr;
+  uint8_t *d_crmask = nullptr;
+  float *d_clean = nullptr, *d_scratch = nullptr;
   int32_t *d_iters = nullptr;
-  CR_TRY(alloc(tot * 4, (void **)&d_data));
-  CR_TRY(hipMemcpyAsync(d_data, data, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (invar) {
-    CR_TRY(alloc(tot * 4, (void **)&d_invar));
-    CR_TRY(hipMemcpyAsync(d_invar, invar, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (inmask) {
-    CR_TRY(alloc(tot, (void **)&d_inmask));
-    CR_TRY(hipMemcpyAsync(d_inmask, inmask, tot, hipMemcpyHostToDevice, ctx->stream));
-  }
-  CR_TRY(alloc(tot, (void **)&d_crmask));
-  if (clean) CR_TRY(alloc(tot * 4, (void **)&d_clean));
-  if (iters) CR_TRY(alloc((size_t)K * 4, (void **)&d_iters));
-  if (const size_t sb = cosmics_scratch_bytes(ctx, K, n)) CR_TRY(alloc(sb, (void **)&d_scratch));
-  CR_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-  CR_TRY(cosmics_launch(ctx, K, n, d_data, d_invar, d_inmask, cfg, d_crmask, d_clean, d_iters, d_scratch));
-  CR_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  CR_TRY(hipMemcpyAsync(crmask, d_crmask, tot, hipMemcpyDeviceToHost, ctx->stream));
-  if (clean) CR_TRY(hipMemcpyAsync(clean, d_clean, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (iters) CR_TRY(hipMemcpyAsync(iters, d_iters, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CR_TRY(hipStreamSynchronize(ctx->stream));
-  if (kernel_ms) CR_TRY(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
-  cleanup();
-#undef CR_TRY
+  LC_HIP(ctx, call.upload(data, tot, &d_data));
+  LC_HIP(ctx, call.upload(invar, tot, &d_invar));
+  LC_HIP(ctx, call.upload(inmask, tot, &d_inmask));
+  LC_HIP(ctx, call.result(crmask, tot, &d_crmask));
+  LC_HIP(ctx, call.result(clean, tot, &d_clean));
+  LC_HIP(ctx, call.result(iters, (size_t)K, &d_iters));
+  if (const size_t sb = cosmics_scratch_bytes(ctx, K, n)) LC_HIP(ctx, call.alloc(sb / 4, &d_scratch));
+  LC_HIP(ctx, call.start());
+  LC_HIP(ctx, cosmics_launch(ctx, K, n, d_data, d_invar, d_inmask, cfg, d_crmask, d_clean, d_iters, d_scratch));
+  LC_HIP(ctx, call.stop());
+  LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;
 }
 

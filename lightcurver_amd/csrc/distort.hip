@@ -6,6 +6,7 @@
 //   A = [[1 + dilation_x, shear], [shear, 1 + dilation_y]];
 //   out[u][v] = bilinear_0(psf, c + A^-1 ((v, u) - c)),  c = (N - 1) // 2 (the zero-lag index: the PSF centre stays
 //   put), bilinear_0 = order-1 interpolation with zeros outside the grid; the result is renormalised to unit sum.
+#include "device_call.h"
 #include "lc_common.h"
 
 using namespace lc;
@@ -65,17 +66,11 @@ extern "C" int lc_apply_distortion(lc_ctx *ctx, int N, int K, const float *narro
     if (!std::isfinite(coeffs[i])) LC_FAIL(ctx, LC_ERR_INVALID, "lc_apply_distortion: non-finite coefficient");
   const size_t NN = (size_t)N * N;
   float *dpsf = nullptr, *dcoef = nullptr, *dxy = nullptr, *dout = nullptr;
-  struct Guard {
-    float **p[4];
-    ~Guard() {
-      for (auto q : p)
-        if (*q) (void)hipFree(*q);
-    }
-  } guard{{&dpsf, &dcoef, &dxy, &dout}};
-  LC_HIP(ctx, hipMalloc((void **)&dpsf, NN * sizeof(float)));
-  LC_HIP(ctx, hipMalloc((void **)&dcoef, 9 * sizeof(float)));
-  LC_HIP(ctx, hipMalloc((void **)&dxy, (size_t)K * 2 * sizeof(float)));
-  LC_HIP(ctx, hipMalloc((void **)&dout, (size_t)K * NN * sizeof(float)));
+  DevPool pool;
+  LC_HIP(ctx, pool.alloc(NN, &dpsf));
+  LC_HIP(ctx, pool.alloc(9, &dcoef));
+  LC_HIP(ctx, pool.alloc((size_t)K * 2, &dxy));
+  LC_HIP(ctx, pool.alloc((size_t)K * NN, &dout));
   hipStream_t q = ctx->stream;
   LC_HIP(ctx, hipMemcpyAsync(dpsf, narrow_psf, NN * sizeof(float), hipMemcpyHostToDevice, q));
   LC_HIP(ctx, hipMemcpyAsync(dcoef, coeffs, 9 * sizeof(float), hipMemcpyHostToDevice, q));

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "device_call.h"
 #include "joint_kernels.h"
 #include "joint_gm.h"
 #include "joint_reduce_peer.h"
@@ -165,16 +166,14 @@ struct lc_joint {
   // F, C [E][M][M], sigma [E][M] one after the other
   float *tmpl = nullptr, *fcov = nullptr;
   int fcov_chunk = 0;
-  std::vector<void *> allocs;
+  DevPool pool;  // everything dmalloc handed out; hist, ghist and phist are grown and freed on their own
 };
 
 namespace {
 
 template <class T>
 int dmalloc(lc_joint *j, T **p, size_t count) {
-  LC_HIP(j->ctx, hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-  j->allocs.push_back(*p);
-  LC_HIP(j->ctx, hipMemsetAsync(*p, 0, std::max<size_t>(count, 1) * sizeof(T), j->ctx->stream));
+  LC_HIP(j->ctx, j->pool.alloc_zeroed(std::max<size_t>(count, 1), p, j->ctx->stream));
   return LC_OK;
 }
 int h2d(lc_joint *j, void *dst, const void *src, size_t bytes) {
@@ -325,18 +324,7 @@ __global__ void joint_scene_kernel(int N, int ss, int M, int e, const float *a, 
 }
 
 int ensure_hist(lc_joint *j, int needed) {
-  if (needed <= j->hist_cap) return LC_OK;
-  const int nc = std::max(needed, 2 * j->hist_cap + 64);
-  float *nh = nullptr;
-  LC_HIP(j->ctx, hipMalloc((void **)&nh, (size_t)nc * sizeof(float)));
-  LC_HIP(j->ctx, hipMemsetAsync(nh, 0, (size_t)nc * sizeof(float), j->ctx->stream));
-  if (j->hist) {
-    LC_HIP(j->ctx, hipMemcpyAsync(nh, j->hist, (size_t)j->hist_cap * sizeof(float), hipMemcpyDeviceToDevice, j->ctx->stream));
-    LC_HIP(j->ctx, hipStreamSynchronize(j->ctx->stream));
-    hipFree(j->hist);
-  }
-  j->hist = nh;
-  j->hist_cap = nc;
+  LC_HIP(j->ctx, grow_history(&j->hist, &j->hist_cap, 1, needed, j->ctx->stream));
   return LC_OK;
 }
 
@@ -1375,7 +1363,6 @@ void lc_joint_destroy(lc_joint *j) {
   for (hipEvent_t ev : j->gevents) hipEventDestroy(ev);
   if (j->evReg) hipEventDestroy(j->evReg);
   if (j->evUpd) hipEventDestroy(j->evUpd);
-  for (void *p : j->allocs) hipFree(p);
   if (j->hist) hipFree(j->hist);
   if (j->ghist) hipFree(j->ghist);
   if (j->phist) hipFree(j->phist);
@@ -2042,13 +2029,9 @@ static int run_adabelief_persistent(lc_joint *j, int n_iter, const lc_adabelief_
   std::vector<float> sched((size_t)n_iter * 3);
   for (int t = 0; t < n_iter; ++t) adabelief_schedule(ab, j->iters_done + t, sched[3 * t], sched[3 * t + 1], sched[3 * t + 2]);
   float *d_sched = nullptr, *d_hist_e = nullptr;
-  LC_HIP(j->ctx, hipMalloc((void **)&d_sched, sched.size() * sizeof(float)));
-  struct DevGuard {
-    void *p;
-    ~DevGuard() { (void)hipFree(p); }
-  } g1{d_sched};
-  LC_HIP(j->ctx, hipMalloc((void **)&d_hist_e, (size_t)j->E * n_iter * sizeof(float)));
-  DevGuard g2{d_hist_e};
+  DevPool scratch;
+  LC_HIP(j->ctx, scratch.alloc(sched.size(), &d_sched));
+  LC_HIP(j->ctx, scratch.alloc((size_t)j->E * n_iter, &d_hist_e));
   LC_HIP(j->ctx, hipMemcpyAsync(d_sched, sched.data(), sched.size() * sizeof(float), hipMemcpyHostToDevice, q));
   JointPsArgs P;
   std::memset(&P, 0, sizeof(P));  // (fields a launch does not use are passed as zeros, not as stack contents)
@@ -2111,19 +2094,7 @@ static int run_adabelief_persistent(lc_joint *j, int n_iter, const lc_adabelief_
 // ---- batched star photometry: every star of the batch advances by one iteration per kernel pair ----------------------------
 namespace {
 int ensure_group_hist(lc_joint *j, int needed) {
-  if (needed <= j->ghist_cap) return LC_OK;
-  const int nc = std::max(needed, 2 * j->ghist_cap + 64);
-  float *nh = nullptr;
-  LC_HIP(j->ctx, hipMalloc((void **)&nh, (size_t)j->G * nc * sizeof(float)));
-  LC_HIP(j->ctx, hipMemsetAsync(nh, 0, (size_t)j->G * nc * sizeof(float), j->ctx->stream));
-  if (j->ghist) {
-    LC_HIP(j->ctx, hipMemcpy2DAsync(nh, (size_t)nc * sizeof(float), j->ghist, (size_t)j->ghist_cap * sizeof(float),
-                                    (size_t)j->ghist_cap * sizeof(float), j->G, hipMemcpyDeviceToDevice, j->ctx->stream));
-    LC_HIP(j->ctx, hipStreamSynchronize(j->ctx->stream));
-    hipFree(j->ghist);
-  }
-  j->ghist = nh;
-  j->ghist_cap = nc;
+  LC_HIP(j->ctx, grow_history(&j->ghist, &j->ghist_cap, j->G, needed, j->ctx->stream));
   return LC_OK;
 }
 // the per-star views of the update arguments (pointers offset to the star's epochs), uploaded before a run
@@ -2294,15 +2265,13 @@ int lc_joint_run_adabelief(lc_joint *j, int n_iter, const lc_adabelief_cfg *cfg)
   // (parameters, both moments: the epoch kernels only read them) - self-healing, like the two-workgroup PSF kernel.
   const bool may_cluster = j->cl_ctr && !j->cluster_off && j->v->ek_cluster;
   const int it0 = j->iters_done, ph0 = j->phist_rows;
-  struct SnapGuard {
-    float *p = nullptr;
-    ~SnapGuard() { if (p) (void)hipFree(p); }
-  } snap;
+  DevPool snap_pool;
+  float *snap = nullptr;
   auto snapshot = [&](bool restore) -> int {
     size_t total = 0;
     for (int k = 0; k < LC_P_COUNT; ++k) total += 3 * (size_t)std::max(j->psize[k], 1);
-    if (!restore) LC_HIP(j->ctx, hipMalloc((void **)&snap.p, total * sizeof(float)));
-    float *c = snap.p;
+    if (!restore) LC_HIP(j->ctx, snap_pool.alloc(total, &snap));
+    float *c = snap;
     for (int k = 0; k < LC_P_COUNT; ++k)
       for (float *blk : {j->par[k], j->pm[k], j->ps[k]}) {
         const size_t cnt = (size_t)std::max(j->psize[k], 1);
@@ -2390,7 +2359,7 @@ int lc_joint_run_adabelief(lc_joint *j, int n_iter, const lc_adabelief_cfg *cfg)
       const unsigned int zero = 0;
       if (err_flag) (void)h2d(j, j->reg_flag + 1, &zero, sizeof(zero));
       if (err_gate) (void)h2d(j, j->upd_ctr + 1, &zero, sizeof(zero));
-      if (may_wait && snap.p && !j->force_events) {
+      if (may_wait && snap && !j->force_events) {
         j->force_events = true;
         j->wait_fallbacks += 1;
         if (std::getenv("LCMI_DEBUG_STREAMS")) std::fprintf(stderr, "lc_joint: an in-kernel wait ran out (flag %u, gate %u): run redone with events\n", err_flag, err_gate);
@@ -2496,16 +2465,9 @@ int lc_joint_run_lbfgs(lc_joint *j, int maxiter, const float *const lower[LC_P_C
   float *buf = nullptr;
   int *order_dev = nullptr;
   const size_t nvec = 7 + 2 * (size_t)kLbMem;
-  LC_HIP(j->ctx, hipMalloc((void **)&buf, (nvec * D + kLbMem + 8) * sizeof(float)));
-  struct Guard {
-    float *b;
-    int **o;
-    ~Guard() {
-      (void)hipFree(b);
-      if (*o) (void)hipFree(*o);
-    }
-  } guard{buf, &order_dev};
-  LC_HIP(j->ctx, hipMalloc((void **)&order_dev, kLbMem * sizeof(int)));
+  DevPool scratch;
+  LC_HIP(j->ctx, scratch.alloc(nvec * D + kLbMem + 8, &buf));
+  LC_HIP(j->ctx, scratch.alloc((size_t)kLbMem, &order_dev));
   // hipMalloc hands back recycled bytes: nothing below reads a vector before writing it, and the work space starts from
   // zeros all the same (LCMI_LBFGS_POISON, a test hook, fills it with NaN patterns instead: the results must not change)
   LC_HIP(j->ctx, hipMemsetAsync(buf, std::getenv("LCMI_LBFGS_POISON") ? 0xFF : 0, (nvec * D + kLbMem + 8) * sizeof(float), q));

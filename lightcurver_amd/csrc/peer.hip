@@ -83,22 +83,25 @@ int lc_peer_group_create(lc_ctx *ctx, int count, int rank, int world, lc_peer_gr
   g->nchunks = (count + kChunk - 1) / kChunk;
   g->cpad = g->nchunks * kChunk;
   g->bytes = (2 * (size_t)g->cpad + 2 * (size_t)g->nchunks) * sizeof(float);
+  // every failure from here on frees what the group holds and names the call that failed
+  auto fail = [&](const char *step, hipError_t e) {
+    ctx->err = std::string("lc_peer_group_create: ") + step + ": " + hipGetErrorString(e);
+    lc_peer_group_destroy(g);
+    return LC_ERR_DEVICE;
+  };
+  const size_t arrive_bytes = (size_t)g->nchunks * sizeof(unsigned int);
   // fine-grained (uncached across devices) where the runtime offers it; plain device memory otherwise
   hipError_t e = hipExtMallocWithFlags((void **)&g->own, g->bytes, hipDeviceMallocFinegrained);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     e = hipMalloc((void **)&g->own, g->bytes);
   }
-  if (e != hipSuccess || hipMalloc((void **)&g->err, sizeof(unsigned int)) != hipSuccess) {
-    ctx->err = std::string("lc_peer_group_create: ") + hipGetErrorString(e);
-    if (g->own) (void)hipFree(g->own);
-    delete g;
-    return LC_ERR_DEVICE;
-  }
-  LC_HIP(ctx, hipMemset(g->own, 0, g->bytes));
-  LC_HIP(ctx, hipMemset(g->err, 0, sizeof(unsigned int)));
-  LC_HIP(ctx, hipMalloc((void **)&g->arrive, (size_t)g->nchunks * sizeof(unsigned int)));
-  LC_HIP(ctx, hipMemset(g->arrive, 0, (size_t)g->nchunks * sizeof(unsigned int)));
+  if (e != hipSuccess) return fail("hipMalloc(own)", e);
+  if ((e = hipMalloc((void **)&g->err, sizeof(unsigned int))) != hipSuccess) return fail("hipMalloc(err)", e);
+  if ((e = hipMemset(g->own, 0, g->bytes)) != hipSuccess) return fail("hipMemset(own)", e);
+  if ((e = hipMemset(g->err, 0, sizeof(unsigned int))) != hipSuccess) return fail("hipMemset(err)", e);
+  if ((e = hipMalloc((void **)&g->arrive, arrive_bytes)) != hipSuccess) return fail("hipMalloc(arrive)", e);
+  if ((e = hipMemset(g->arrive, 0, arrive_bytes)) != hipSuccess) return fail("hipMemset(arrive)", e);
   g->peer[rank] = g->own;
   *out = g;
   return LC_OK;

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "device_call.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -26,7 +27,7 @@ struct PrepArgs {
   float nan_noise, boost;
   int boost_whole_stamp;
   float *data_out, *noisemap_out, *weight_out;
-  int *masked_count;
+  int32_t *masked_count;
 };
 
 __device__ __forceinline__ void prep_pixel(const PrepArgs &A, int k, size_t idx, float inv_coef, float t, float trms2,
@@ -122,27 +123,9 @@ int lc_prepare_stamps(lc_ctx *ctx, int K, int npix, const float *data, const flo
   if (K <= 0 || npix <= 0 || !data) LC_FAIL(ctx, LC_ERR_INVALID, "lc_prepare_stamps: invalid argument");
   if (!noisemap && !(rms && exptime))
     LC_FAIL(ctx, LC_ERR_INVALID, "lc_prepare_stamps: without a noise map, rms and exptime are required");
-  LC_HIP(ctx, hipSetDevice(ctx->device));
+  LC_ENTER(ctx);
   const size_t tot = (size_t)K * npix;
-  std::vector<void *> dev;
-  auto up = [&](const void *h, size_t bytes, void **d) -> hipError_t {
-    hipError_t e = hipMalloc(d, bytes);
-    if (e != hipSuccess) return e;
-    dev.push_back(*d);
-    return h ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
-  };
-  auto cleanup = [&]() {
-    for (void *p : dev) (void)hipFree(p);
-  };
-#define PREP_TRY(call)                                                \
-  do {                                                                \
-    hipError_t e_ = (call);                                           \
-    if (e_ != hipSuccess) {                                           \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);   \
-      cleanup();                                                      \
-      return LC_ERR_DEVICE;                                           \
-    }                                                                 \
-  } while (0)
+  DeviceCall call(ctx);
   PrepArgs A;
   std::memset(&A, 0, sizeof(A));
   A.K = K;
@@ -150,68 +133,35 @@ int lc_prepare_stamps(lc_ctx *ctx, int K, int npix, const float *data, const flo
   A.nan_noise = nan_noise;
   A.boost = noise_boost;
   A.boost_whole_stamp = boost_whole_stamp;
-  void *p = nullptr;
-  PREP_TRY(up(data, tot * 4, &p));
-  A.data = (const float *)p;
+  LC_HIP(ctx, call.upload(data, tot, &A.data));
   if (noisemap) {
-    PREP_TRY(up(noisemap, tot * 4, &p));
-    A.noisemap = (const float *)p;
+    LC_HIP(ctx, call.upload(noisemap, tot, &A.noisemap));
   } else {
-    PREP_TRY(up(rms, (size_t)K * 4, &p));
-    A.rms = (const float *)p;
-    PREP_TRY(up(exptime, (size_t)K * 4, &p));
-    A.exptime = (const float *)p;
+    LC_HIP(ctx, call.upload(rms, (size_t)K, &A.rms));
+    LC_HIP(ctx, call.upload(exptime, (size_t)K, &A.exptime));
   }
-  if (coefficient) {
-    PREP_TRY(up(coefficient, (size_t)K * 4, &p));
-    A.coefficient = (const float *)p;
-  }
-  if (bad) {
-    PREP_TRY(up(bad, tot, &p));
-    A.bad = (const uint8_t *)p;
-  }
-  if (data_out) {
-    PREP_TRY(up(nullptr, tot * 4, &p));
-    A.data_out = (float *)p;
-  }
-  if (noisemap_out) {
-    PREP_TRY(up(nullptr, tot * 4, &p));
-    A.noisemap_out = (float *)p;
-  }
-  if (weight_out) {
-    PREP_TRY(up(nullptr, tot * 4, &p));
-    A.weight_out = (float *)p;
-  }
-  if (masked_count) {
-    PREP_TRY(up(nullptr, (size_t)K * 4, &p));
-    A.masked_count = (int *)p;
-  }
-  PREP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  LC_HIP(ctx, call.upload(coefficient, (size_t)K, &A.coefficient));
+  LC_HIP(ctx, call.upload(bad, tot, &A.bad));
+  LC_HIP(ctx, call.result(data_out, tot, &A.data_out));
+  LC_HIP(ctx, call.result(noisemap_out, tot, &A.noisemap_out));
+  LC_HIP(ctx, call.result(weight_out, tot, &A.weight_out));
+  LC_HIP(ctx, call.result(masked_count, (size_t)K, &A.masked_count));
+  LC_HIP(ctx, call.start());
   hipLaunchKernelGGL(prep_stamps_kernel, dim3(K), dim3(kPrepThreads), 0, ctx->stream, A);
-  PREP_TRY(hipGetLastError());
-  PREP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  if (data_out) PREP_TRY(hipMemcpyAsync(data_out, A.data_out, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (noisemap_out) PREP_TRY(hipMemcpyAsync(noisemap_out, A.noisemap_out, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (weight_out) PREP_TRY(hipMemcpyAsync(weight_out, A.weight_out, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (masked_count)
-    PREP_TRY(hipMemcpyAsync(masked_count, A.masked_count, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
-  PREP_TRY(hipStreamSynchronize(ctx->stream));
-  if (kernel_ms) PREP_TRY(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
-  cleanup();
-#undef PREP_TRY
+  LC_HIP(ctx, hipGetLastError());
+  LC_HIP(ctx, call.stop());
+  LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;
 }
 
 int lc_copy_bandwidth(lc_ctx *ctx, int64_t bytes, int reps, float *gb_per_s) {
   if (!ctx || !gb_per_s || bytes < 1024 || reps <= 0) return LC_ERR_INVALID;
-  LC_HIP(ctx, hipSetDevice(ctx->device));
+  LC_ENTER(ctx);
   const size_t n4 = (size_t)bytes / 16;
+  DevPool pool;
   float4 *a = nullptr, *b = nullptr;
-  LC_HIP(ctx, hipMalloc((void **)&a, n4 * 16));
-  if (hipMalloc((void **)&b, n4 * 16) != hipSuccess) {
-    (void)hipFree(a);
-    LC_FAIL(ctx, LC_ERR_DEVICE, "lc_copy_bandwidth: out of memory");
-  }
+  LC_HIP(ctx, pool.alloc(n4, &a));
+  LC_HIP(ctx, pool.alloc(n4, &b));
   (void)hipMemsetAsync(a, 0, n4 * 16, ctx->stream);
   const int blocks = ctx->n_cu > 0 ? ctx->n_cu * 8 : 2048;
   hipLaunchKernelGGL(copy_kernel, dim3(blocks), dim3(256), 0, ctx->stream, a, b, n4);  // warm-up
@@ -221,8 +171,6 @@ int lc_copy_bandwidth(lc_ctx *ctx, int64_t bytes, int reps, float *gb_per_s) {
   hipError_t e = hipStreamSynchronize(ctx->stream);
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-  (void)hipFree(a);
-  (void)hipFree(b);
   if (e != hipSuccess) LC_FAIL(ctx, LC_ERR_DEVICE, std::string("lc_copy_bandwidth: ") + hipGetErrorString(e));
   *gb_per_s = (float)(2.0 * (double)n4 * 16.0 * reps / (ms * 1e-3) / 1e9);  // read + write
   return LC_OK;

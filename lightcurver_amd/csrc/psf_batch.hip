@@ -1,7 +1,9 @@
 // PSF-fit batch object behind the C ABI (include/lcmi.h, "PSF fit" section).
 #include <cmath>
 #include <cstring>
+#include <memory>
 
+#include "device_call.h"
 #include "lbfgs_host.h"
 #include <thread>
 
@@ -47,16 +49,14 @@ struct lc_psf_batch {
   bool have_W = false;
   float lam_sc = 0.f, lam_hf = 0.f;
   int hist_stride = 0, iters_done = 0;
-  std::vector<void *> allocs;
+  DevPool pool;  // everything dmalloc handed out; hist is grown and freed on its own
 };
 
 namespace {
 
 template <class T>
 int dmalloc(lc_psf_batch *b, T **p, size_t count) {
-  LC_HIP(b->ctx, hipMalloc((void **)p, count * sizeof(T)));
-  b->allocs.push_back(*p);
-  LC_HIP(b->ctx, hipMemsetAsync(*p, 0, count * sizeof(T), b->ctx->stream));
+  LC_HIP(b->ctx, b->pool.alloc_zeroed(count, p, b->ctx->stream));
   return LC_OK;
 }
 
@@ -382,19 +382,7 @@ int read_split_fallbacks(lc_psf_batch *b, int *count) {
 }
 
 int ensure_hist(lc_psf_batch *b, int needed) {
-  if (needed <= b->hist_stride) return LC_OK;
-  int ns = std::max(needed, 2 * b->hist_stride + 64);
-  float *nh = nullptr;
-  LC_HIP(b->ctx, hipMalloc((void **)&nh, (size_t)b->F * ns * sizeof(float)));
-  LC_HIP(b->ctx, hipMemsetAsync(nh, 0, (size_t)b->F * ns * sizeof(float), b->ctx->stream));
-  if (b->hist) {
-    LC_HIP(b->ctx, hipMemcpy2DAsync(nh, ns * sizeof(float), b->hist, b->hist_stride * sizeof(float),
-                                     b->hist_stride * sizeof(float), b->F, hipMemcpyDeviceToDevice, b->ctx->stream));
-    LC_HIP(b->ctx, hipStreamSynchronize(b->ctx->stream));
-    hipFree(b->hist);
-  }
-  b->hist = nh;
-  b->hist_stride = ns;
+  LC_HIP(b->ctx, grow_history(&b->hist, &b->hist_stride, b->F, needed, b->ctx->stream));
   return LC_OK;
 }
 
@@ -490,7 +478,6 @@ void lc_psf_batch_destroy(lc_psf_batch *b) {
   if (!b) return;
   (void)hipSetDevice(b->ctx->device);
   hipStreamSynchronize(b->ctx->stream);
-  for (void *p : b->allocs) hipFree(p);
   if (b->hist) hipFree(b->hist);
   delete b;
 }
@@ -792,13 +779,9 @@ int lc_psf_batch_fit_moffat(lc_psf_batch *b, int n_iter, float *final_loss) {
     int *ints = nullptr;
     const size_t n_dbl = 6 * FD + 2 * FD * kPsfLbfgsMem + (size_t)F * kPsfLbfgsMem + 2 * (size_t)F;
     const size_t n_int = 4 * (size_t)F + (size_t)max_rounds + 1;
-    LC_HIP(b->ctx, hipMalloc((void **)&dbl, n_dbl * sizeof(double)));
-    struct DevGuard {
-      void *p;
-      ~DevGuard() { (void)hipFree(p); }
-    } g1{dbl};
-    LC_HIP(b->ctx, hipMalloc((void **)&ints, n_int * sizeof(int)));
-    DevGuard g2{ints};
+    DevPool scratch;
+    LC_HIP(b->ctx, scratch.alloc(n_dbl, &dbl));
+    LC_HIP(b->ctx, scratch.alloc(n_int, &ints));
     LC_HIP(b->ctx, hipMemsetAsync(dbl, 0, n_dbl * sizeof(double), q));
     LC_HIP(b->ctx, hipMemsetAsync(ints, 0, n_int * sizeof(int), q));
     PsfLbfgsDev P;
@@ -868,10 +851,7 @@ int lc_psf_batch_fit_moffat(lc_psf_batch *b, int n_iter, float *final_loss) {
   const size_t n_in = (size_t)F * 4 + (size_t)F * S * 4, n_out = (size_t)F + (size_t)F * 4 + (size_t)F * S * 4;
   float *pin = nullptr;
   LC_HIP(b->ctx, hipHostMalloc((void **)&pin, (n_in + n_out) * sizeof(float), hipHostMallocDefault));
-  struct PinGuard {
-    float *p;
-    ~PinGuard() { (void)hipHostFree(p); }
-  } guard{pin};
+  const std::unique_ptr<float, decltype(&hipHostFree)> pinned(pin, hipHostFree);  // freed on every exit path
   float *pmof = pin, *pst = pin + (size_t)F * 4, *loss = pin + n_in, *gm = loss + F, *gs = gm + (size_t)F * 4;
   std::memcpy(pst, st.data(), st.size() * sizeof(float));  // sky (column 3) stays as it is
   auto eval = [&](const std::vector<double> &X, std::vector<double> &Fv, std::vector<double> &G) -> int {

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <vector>
 
+#include "device_call.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -583,24 +584,7 @@ int lc_segment_stamps(lc_ctx *ctx, int K, int n, const float *data, const float 
     LC_FAIL(ctx, LC_ERR_INVALID, "lc_segment_stamps: thresh must be positive and deblend_cont non-negative");
   LC_ENTER(ctx);
   const size_t np = (size_t)n * n, tot = (size_t)K * np;
-  std::vector<void *> dev;
-  auto cleanup = [&]() {
-    for (void *p : dev) (void)hipFree(p);
-  };
-  auto alloc = [&](size_t bytes, void **d) -> hipError_t {
-    hipError_t e = hipMalloc(d, bytes);
-    if (e == hipSuccess) dev.push_back(*d);
-    return e;
-  };
-#define SEG_TRY(call)                                             \
-  do {                                                            \
-    hipError_t e_ = (call);                                       \
-    if (e_ != hipSuccess) {                                       \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-      cleanup();                                                  \
-      return LC_ERR_DEVICE;                                       \
-    }                                                             \
-  } while (0)
+  DeviceCall call(ctx);
   SegArgs A;
   std::memset(&A, 0, sizeof(A));
   A.K = K;
@@ -610,48 +594,21 @@ int lc_segment_stamps(lc_ctx *ctx, int K, int n, const float *data, const float 
   A.clean = cfg->clean != 0;
   A.thresh = cfg->thresh;
   A.cont = (double)cfg->deblend_cont;
-  void *p = nullptr;
-  SEG_TRY(alloc(tot * 4, &p));
-  A.data = (const float *)p;
-  SEG_TRY(hipMemcpyAsync(p, data, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-  SEG_TRY(alloc(tot * 4, &p));
-  A.noise = (const float *)p;
-  SEG_TRY(hipMemcpyAsync(p, noisemap, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-  SEG_TRY(alloc(tot, &p));
-  A.mask = (uint8_t *)p;
-  if (segmap) {
-    SEG_TRY(alloc(tot * 4, &p));
-    A.segmap = (int32_t *)p;
-  }
-  if (nobj) {
-    SEG_TRY(alloc((size_t)K * 4, &p));
-    A.nobj = (int32_t *)p;
-  }
-  if (status) {
-    SEG_TRY(alloc((size_t)K * 4, &p));
-    A.status = (int32_t *)p;
-  }
-  const size_t xy_bytes = (size_t)K * kSegObjCap * 2 * 4;
-  if (xy) {
-    SEG_TRY(alloc(xy_bytes, &p));
-    A.xy = (float *)p;
-  }
+  LC_HIP(ctx, call.upload(data, tot, &A.data));
+  LC_HIP(ctx, call.upload(noisemap, tot, &A.noise));
+  LC_HIP(ctx, call.result(mask, tot, &A.mask));
+  LC_HIP(ctx, call.result(segmap, tot, &A.segmap));
+  LC_HIP(ctx, call.result(nobj, (size_t)K, &A.nobj));
+  LC_HIP(ctx, call.result(status, (size_t)K, &A.status));
+  LC_HIP(ctx, call.result(xy, (size_t)K * kSegObjCap * 2, &A.xy));
   const size_t lds_bytes = seg_plane_bytes(n);
-  SEG_TRY(hipFuncSetAttribute((const void *)segment_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_bytes));
-  SEG_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  LC_HIP(ctx, hipFuncSetAttribute((const void *)segment_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_bytes));
+  LC_HIP(ctx, call.start());
   hipLaunchKernelGGL(segment_kernel, dim3(K), dim3(kSegThreads), lds_bytes, ctx->stream, A);
-  SEG_TRY(hipGetLastError());
-  SEG_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  SEG_TRY(hipMemcpyAsync(mask, A.mask, tot, hipMemcpyDeviceToHost, ctx->stream));
-  if (segmap) SEG_TRY(hipMemcpyAsync(segmap, A.segmap, tot * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (nobj) SEG_TRY(hipMemcpyAsync(nobj, A.nobj, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (status) SEG_TRY(hipMemcpyAsync(status, A.status, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (xy) SEG_TRY(hipMemcpyAsync(xy, A.xy, xy_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  SEG_TRY(hipStreamSynchronize(ctx->stream));
-  if (kernel_ms) SEG_TRY(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
-  cleanup();
-#undef SEG_TRY
+  LC_HIP(ctx, hipGetLastError());
+  LC_HIP(ctx, call.stop());
+  LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;
 }
 

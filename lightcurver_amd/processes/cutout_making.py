@@ -10,6 +10,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import per_shape
 from .. import _lib
 from ..astroscrappy import _cfg as _cosmics_cfg, _refuse as _refuse_cosmics, detect_cosmics
 from ..ccdproc import _cfg as _ccdmask_cfg
@@ -27,18 +28,7 @@ def mask_cosmics_batch(cutouts, noisemaps, cosmics_masking_params=None, do_mask_
     if isinstance(cutouts, np.ndarray) and cutouts.ndim == 3:
         nm = np.asarray(noisemaps, dtype=np.float32)
         return detect_cosmics(np.asarray(cutouts, dtype=np.float32), invar=nm ** 2, ctx=ctx, **params)[0]
-    cutouts = [np.asarray(c, dtype=np.float32) for c in cutouts]
-    noisemaps = [np.asarray(m, dtype=np.float32) for m in noisemaps]
-    if len(cutouts) != len(noisemaps):
-        raise ValueError('one noise map per cutout')
-    out = [None] * len(cutouts)
-    for shape in sorted({c.shape for c in cutouts}):
-        idx = [i for i, c in enumerate(cutouts) if c.shape == shape]
-        nm = np.stack([noisemaps[i] for i in idx])
-        masks = detect_cosmics(np.stack([cutouts[i] for i in idx]), invar=nm ** 2, ctx=ctx, **params)[0]
-        for i, m in zip(idx, masks):
-            out[i] = m
-    return out
+    return per_shape(lambda d, nm: detect_cosmics(d, invar=nm ** 2, ctx=ctx, **params)[0], cutouts, noisemaps)
 
 
 def _mask_cutouts(d, nm, do_bad_columns, do_cosmics, params, ctx):
@@ -82,15 +72,5 @@ def mask_cutout_batch(cutouts, noisemaps, do_mask_bad_columns, do_mask_cosmics, 
     params = dict(cosmics_masking_params or {})
     if isinstance(cutouts, np.ndarray) and cutouts.ndim == 3:
         return _mask_cutouts(cutouts, noisemaps, do_mask_bad_columns, do_mask_cosmics, params, ctx)
-    cutouts = [np.asarray(c, dtype=np.float32) for c in cutouts]
-    noisemaps = [np.asarray(m, dtype=np.float32) for m in noisemaps]
-    if len(cutouts) != len(noisemaps):
-        raise ValueError('one noise map per cutout')
-    out = [None] * len(cutouts)
-    for shape in sorted({c.shape for c in cutouts}):
-        idx = [i for i, c in enumerate(cutouts) if c.shape == shape]
-        masks = _mask_cutouts(np.stack([cutouts[i] for i in idx]), np.stack([noisemaps[i] for i in idx]),
-                              do_mask_bad_columns, do_mask_cosmics, dict(params), ctx)
-        for i, m in zip(idx, masks):
-            out[i] = m
-    return out
+    return per_shape(lambda d, nm: _mask_cutouts(d, nm, do_mask_bad_columns, do_mask_cosmics, dict(params), ctx),
+                     cutouts, noisemaps)

@@ -5,6 +5,7 @@ from regions.h5 is in ``lightcurver_amd/io/regions.py``, the source masking of :
 and the sqlite bookkeeping stay with the caller (out of scope)."""
 import numpy as np
 
+from . import per_shape
 from ..starred.procedures.psf_routines import build_psf_batch
 
 
@@ -37,27 +38,23 @@ def mask_surrounding_stars_batch(datas, noisemaps, thresh=3.0, minarea=15, deble
     iteration bound, value outside the fixed-point range)."""
     from .source_masking import segment_batch
     stack = isinstance(datas, np.ndarray) and datas.ndim == 3
+    kw = dict(thresh=thresh, minarea=minarea, deblend_cont=deblend_cont)
+
+    def on_device(d, nm):   # None for a stamp that is left to the host
+        if d.ndim != 3 or d.shape[1] != d.shape[2]:
+            raise ValueError(f'square stamps expected, got {d.shape[1:]}')
+        if d.shape[1] > 64:
+            return [None] * len(d)
+        r = segment_batch(d, nm, ctx=ctx, **kw)
+        return [m if st == 0 else None for m, st in zip(r['mask'], r['status'])]
+
     ds = [np.asarray(c, dtype=np.float32) for c in datas]
     ns = [np.asarray(m, dtype=np.float32) for m in noisemaps]
-    if len(ds) != len(ns):
-        raise ValueError('one noise map per stamp')
-    kw = dict(thresh=thresh, minarea=minarea, deblend_cont=deblend_cont)
-    out, n_host = [None] * len(ds), 0
-    for shape in sorted({c.shape for c in ds}):
-        idx = [i for i, c in enumerate(ds) if c.shape == shape]
-        if len(shape) != 2 or shape[0] != shape[1]:
-            raise ValueError(f'square stamps expected, got {shape}')
-        if shape[0] > 64:
-            todo = idx
-        else:
-            r = segment_batch(np.stack([ds[i] for i in idx]), np.stack([ns[i] for i in idx]), ctx=ctx, **kw)
-            for i, m in zip(idx, r['mask']):
-                out[i] = m
-            todo = [i for i, st in zip(idx, r['status']) if st != 0]
-        for i in todo:
-            out[i] = mask_surrounding_stars(ds[i], ns[i], **kw)
-        n_host += len(todo)
-    return (np.stack(out) if stack and out else out), n_host
+    out = per_shape(on_device, ds, ns)
+    todo = [i for i, m in enumerate(out) if m is None]
+    for i in todo:
+        out[i] = mask_surrounding_stars(ds[i], ns[i], **kw)
+    return (np.stack(out) if stack and out else out), len(todo)
 
 
 def prepare_psf_stamps(datas, noisemaps, cosmics_masks, automatic_masks=None, mask_threshold_fraction=0.4):

@@ -189,6 +189,33 @@ int lc_align_stack(lc_ctx *ctx, int C, int E, int n, const float *cubes /* [C][E
                    float *median /* nullable [C][n][n] */, int32_t *n_rejected /* nullable [C][n][n] */,
                    float *kernel_ms /* nullable */);
 
+/* ---- sky background of whole frames: replaces sep.Background inside subtract_background ---------------
+ * Reference call site: lightcurver/processes/background_estimation.py:25 (called at frame_importation.py:81-91):
+ * sep.Background(image, bw=box, bh=box, fw=3, fh=3), image - bkg, bkg.globalrms.  SExtractor's mesh background as frozen
+ * in DESIGN.md section 5 "Sky background": per mesh of bw x bh pixels the clipped moments, the histogram and its mode;
+ * bad meshes filled from the nearest good ones; the fw x fh median of the mesh values; globalback / globalrms the medians
+ * of the filtered meshes; the map a natural bicubic spline through the mesh values; sub = data - back.
+ *   data [K][h][w]; mask [K][h][w], non-zero = ignore (a non-finite pixel is ignored as well).
+ *   nx = (w - 1) / bw + 1, ny = (h - 1) / bh + 1.  Outputs: sub, back [K][h][w]; mesh_back, mesh_rms [K][ny][nx] (after the
+ *   median filter); globalback, globalrms [K]; status [K]: 0, or LC_ERR_NONFINITE for a frame without one good mesh (its
+ *   outputs are NaN, the other frames of the call are not affected); kernel_ms = device time of all kernels (HIP events).
+ * Any h, w >= 1, any K; fw = fh = 1 or 3, fthresh = 0, nx and ny <= 256 and nx * ny <= 2048 (lc_background_supported, no
+ * device needed; LC_ERR_UNSUPPORTED otherwise).  LC_ERR_INVALID: K, h, w, bw or bh < 1, fthresh not finite.
+ * lc_background_map evaluates the same spline through any mesh values (bkg.rms() of sep: the spline through mesh_rms). */
+typedef struct {
+  int32_t bw, bh; /* mesh size in pixels; the reference: min(h, w) / 10 for both */
+  int32_t fw, fh; /* 3, 3 (1, 1: no filter) */
+  float fthresh;  /* 0.0 (the only one built) */
+} lc_background_cfg;
+int lc_background_supported(int h, int w, int bw, int bh, int fw, int fh);
+int lc_background_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const uint8_t *mask /*nullable*/,
+                         const lc_background_cfg *cfg, float *sub /*nullable*/, float *back /*nullable*/,
+                         float *mesh_back /*nullable [K][ny][nx]*/, float *mesh_rms /*nullable [K][ny][nx]*/,
+                         float *globalback /*[K]*/, float *globalrms /*[K]*/, int32_t *status /*[K] nullable*/,
+                         float *kernel_ms /*nullable*/);
+int lc_background_map(lc_ctx *ctx, int K, int h, int w, int bw, int bh, const float *mesh /*[K][ny][nx]*/,
+                      float *map /*[K][h][w]*/, float *kernel_ms /*nullable*/);
+
 /* ---- optimiser settings shared by both fits ----------------------------------------------- */
 /* optax.adabelief as driven by STARRED's Optimizer(method='adabelief'):
  * lightcurver/processes/star_photometry.py:113-122, roi_modelling.py:326-334. */

@@ -60,6 +60,10 @@ class StackCfg(C.Structure):
     _fields_ = [('n_sigma', C.c_float), ('clip', C.c_int32)]
 
 
+class BackgroundCfg(C.Structure):
+    _fields_ = [('bw', C.c_int32), ('bh', C.c_int32), ('fw', C.c_int32), ('fh', C.c_int32), ('fthresh', C.c_float)]
+
+
 SEGMENT_MAX_OBJECTS = 32   # LC_SEGMENT_MAX_OBJECTS of include/lcmi.h
 
 # every symbol include/lcmi.h declares: name -> (restype, argtypes)
@@ -87,6 +91,10 @@ SIGNATURES = {
     'lc_align_stack_supported': (C.c_int, [C.c_int]),
     'lc_align_stack': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, dp, dp, C.POINTER(StackCfg), fp, fp, fp, ip,
                                  C.POINTER(C.c_float)]),
+    'lc_background_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'lc_background_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, C.POINTER(C.c_uint8), C.POINTER(BackgroundCfg), fp,
+                                       fp, fp, fp, fp, fp, ip, C.POINTER(C.c_float)]),
+    'lc_background_map': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_float)]),
     'lc_ctx_stream': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     'lc_ctx_synchronize': (C.c_int, [vp]),
     'lc_timer_start': (C.c_int, [vp]),

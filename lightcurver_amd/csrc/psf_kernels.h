@@ -8,6 +8,7 @@
 // the two transposed passes.  T = Moffat + B, the per-star intermediates and the weighted
 // residuals live in LDS; B's chi2 gradient stays in registers through the starlet phase.
 #pragma once
+#include <type_traits>
 #include <utility>
 
 #include "lc_common.h"
@@ -15,6 +16,15 @@
 
 #ifndef LC_XPOLL_SLEEP
 #define LC_XPOLL_SLEEP 2
+#endif
+// Debugging aids, like LC_XPOLL_SLEEP above: no test and no shipped build sets them.  They rebuild one of the two items of
+// DESIGN.md, "PSF fit: role 0's row pass a star ahead", without the other, for the A / B runs recorded there
+// (make alt ALTFLAGS=-DLC_P5_AHEAD=0).
+#ifndef LC_P5_AHEAD
+#define LC_P5_AHEAD 1  // C2, two workgroups: the transposed row pass requests its operands a star ahead
+#endif
+#ifndef LC_STARLET_LIVE_ADDR
+#define LC_STARLET_LIVE_ADDR 1  // two workgroups, pixel state in registers: the starlet keeps its transpose addresses live
 #endif
 namespace lc {
 constexpr int kXFlagStride = 16;   // flag words per (frame, role): word 0 is the flag, the rest keeps (frame, role) pairs on lines of their own
@@ -840,41 +850,134 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         // same pixels and summed over the frame, is dchi2/dx0 / (amp * SS) of the star (the adjoint form of the
         // x-derivative filter of the forward pass: same number, no second row pass, no second column pass).
         constexpr int WJ = (PX - 1 + NT - 1) / SS + 1;
-        for (int sl = 0; sl < SG; ++sl) {
-          const int s = g0 + sl;
-          if (s >= S) break;
-          progress_prio((4 * sl) / SG);  // (SG stars in four steps)
-          const float *tx = TAPS + (s * 4 + 0) * NTP, *dtx = tx + NTP;
-          const int bq = BQ[s * 2 + 0];
-          const float amp = SP[s * 4 + 0];
-          lc_v2f txd[NT];  // (value tap, derivative tap) pairs of this star, in registers for the whole window
+        // Two workgroups per frame at 8 pixels per thread (C2): the operands of a star - its window of V (a dependent address
+        // chain: base and clamp from BQ), the amplitude and the (value, derivative) tap pairs - are requested one star ahead,
+        // into the second of two register sets, among the multiply-adds of the star before: both waves of a SIMD run this
+        // loop in near lock-step, so nothing else hides the LDS round trips at the head of a star.  The last star of a group
+        // (and star S - 1) requests nothing: no read beyond star S - 1.  Every other instantiation has no registers for a
+        // second set (3 or 4 waves per SIMD, or the one-workgroup form's budget) and asks for everything at the head.
+        constexpr bool AHEAD = SPLIT && PX == 8 && LC_P5_AHEAD;
+        if constexpr (AHEAD) {
+          static_assert(SG % 8 == 0, "two stars per turn of the loop share a priority step");
+          struct P5Ops {
+            float vwin[WJ];  // window of V
+            lc_v2f txd[NT];  // (value tap, derivative tap) pairs of the star, in registers for the whole window
+            float amp;
+          };
+          // the multiply-adds of star sl from `use`, its share of gB and of the x0 gradient; on_the_way() runs behind the fourth
+          // window sample (the look-ahead form requests the next star's taps there)
+          auto p5_star = [&](int sl, const P5Ops &use, auto on_the_way) {
+            const int s = g0 + sl;
+            lc_v2f accp[PX];
 #pragma unroll
-          for (int k = 0; k < NT; ++k) txd[k] = TAPP[(s * 2 + 0) * NT + k];
-          lc_v2f accp[PX];
+            for (int p = 0; p < PX; ++p) accp[p] = (lc_v2f){0.f, 0.f};
 #pragma unroll
-          for (int p = 0; p < PX; ++p) accp[p] = (lc_v2f){0.f, 0.f};
-          const float *vrow = V + (sl * N + pu) * C::VS + 1;
-          const int jd0 = bq + pv / SS;
-          float vwin[WJ];
+            for (int i = 0; i < WJ; ++i) {
+              if (i == 4) on_the_way();
+              const lc_v2f vv = pk_bcast(use.vwin[i]);
 #pragma unroll
-          for (int i = 0; i < WJ; ++i) vwin[i] = vrow[min(max(jd0 + i, -1), n)];
-#pragma unroll
-          for (int i = 0; i < WJ; ++i) {
-            const lc_v2f vv = pk_bcast(vwin[i]);
-#pragma unroll
-            for (int k = 0; k < NT; ++k) {
-              const int rel = SS * i - k;
-              if (rel >= 0 && rel < PX) accp[rel] = pk_fma(txd[k], vv, accp[rel]);
+              for (int k = 0; k < NT; ++k) {
+                const int rel = SS * i - k;
+                if (rel >= 0 && rel < PX) accp[rel] = pk_fma(use.txd[k], vv, accp[rel]);
+              }
             }
-          }
-          float gxs = 0.f;
+            float gxs = 0.f;
 #pragma unroll
-          for (int p = 0; p < PX; ++p) {
-            gB[p] = fmaf(amp, accp[p].x, gB[p]);
-            gxs = fmaf(accp[p].y, tpix[p], gxs);
+            for (int p = 0; p < PX; ++p) {
+              gB[p] = fmaf(use.amp, accp[p].x, gB[p]);
+              gxs = fmaf(accp[p].y, tpix[p], gxs);
+            }
+            gxs = wave_sum(gxs);
+            if (lane == 0) REDX[s * C::NW + wid] = gxs;
+          };
+          auto nothing = [] {};
+          // The request is made in two parts, each pinned where it stands (the scheduler otherwise sinks the reads behind the
+          // multiply-adds, to save registers): window and amplitude in front of the multiply-adds, the taps behind the first
+          // few window samples.  At most 15 LDS reads can be counted as outstanding, so with all 19 in front the multiply-adds
+          // would wait for the first of the reads they are meant to overlap.
+          auto p5_window = [&](int sl, P5Ops &o, int bq) {
+            o.amp = SP[(g0 + sl) * 4 + 0];
+            const float *vrow = V + (sl * N + pu) * C::VS + 1;
+            const int jd0 = bq + pv / SS;
+#pragma unroll
+            for (int i = 0; i < WJ; ++i) o.vwin[i] = vrow[min(max(jd0 + i, -1), n)];
+            __builtin_amdgcn_sched_barrier(0);
+          };
+          auto p5_taps = [&](int sl, P5Ops &o) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < NT; ++k) o.txd[k] = TAPP[((g0 + sl) * 2 + 0) * NT + k];
+            __builtin_amdgcn_sched_barrier(0);
+          };
+          // A request never sits under a condition of its own: behind a branch the compiler's wait counts assume the shorter
+          // path and make the multiply-adds wait for the very reads they overlap.  So the loop body serves the stars that have
+          // a successor and the last star follows the loop.  The window base of a star (BQ) is read one star further ahead
+          // still, so that the address chain starts from a register, at a star index clamped to S - 1.
+          const int ns = min(SG, S - g0);  // stars of this group (>= 1)
+          P5Ops opsA, opsB;
+          int bqn = BQ[min(g0 + 1, S - 1) * 2 + 0];
+          p5_window(0, opsA, BQ[g0 * 2 + 0]);
+          p5_taps(0, opsA);
+          int sl = 0;
+          // (not peeled or unrolled: each copy of the body holds the clamped window addresses of two stars)
+#pragma clang loop unroll(disable)
+          while (sl + 1 < ns) {
+            progress_prio((4 * sl) / SG);  // (SG stars in four steps)
+            const int bqnn = BQ[min(g0 + sl + 2, S - 1) * 2 + 0];
+            p5_window(sl + 1, opsB, bqn);
+            p5_star(sl, opsA, [&] { p5_taps(sl + 1, opsB); });
+            if (sl + 2 >= ns) {
+              opsA = opsB;
+              sl += 1;
+              break;
+            }
+            bqn = BQ[min(g0 + sl + 3, S - 1) * 2 + 0];
+            p5_window(sl + 2, opsA, bqnn);
+            p5_star(sl + 1, opsB, [&] { p5_taps(sl + 2, opsA); });
+            sl += 2;
           }
-          gxs = wave_sum(gxs);
-          if (lane == 0) REDX[s * C::NW + wid] = gxs;
+          progress_prio((4 * sl) / SG);
+          p5_star(sl, opsA, nothing);
+        } else {
+          // (The arithmetic of a star is spelled out here a second time on purpose: routed through p5_star, with the operands
+          // read in this very order, the kernels at 4 pixels per thread come out with other registers - 120 -> 128 at N = 16,
+          // three spilled at N = 48 two-workgroup.  This form gives them the assembly they had; tests/test_psf_budget_bits_gpu.py
+          // holds both copies to the same bits.)
+          for (int sl = 0; sl < SG; ++sl) {
+            const int s = g0 + sl;
+            if (s >= S) break;
+            progress_prio((4 * sl) / SG);  // (SG stars in four steps)
+            const int bq = BQ[s * 2 + 0];
+            const float amp = SP[s * 4 + 0];
+            lc_v2f txd[NT];  // (value tap, derivative tap) pairs of this star, in registers for the whole window
+#pragma unroll
+            for (int k = 0; k < NT; ++k) txd[k] = TAPP[(s * 2 + 0) * NT + k];
+            lc_v2f accp[PX];
+#pragma unroll
+            for (int p = 0; p < PX; ++p) accp[p] = (lc_v2f){0.f, 0.f};
+            const float *vrow = V + (sl * N + pu) * C::VS + 1;
+            const int jd0 = bq + pv / SS;
+            float vwin[WJ];
+#pragma unroll
+            for (int i = 0; i < WJ; ++i) vwin[i] = vrow[min(max(jd0 + i, -1), n)];
+#pragma unroll
+            for (int i = 0; i < WJ; ++i) {
+              const lc_v2f vv = pk_bcast(vwin[i]);
+#pragma unroll
+              for (int k = 0; k < NT; ++k) {
+                const int rel = SS * i - k;
+                if (rel >= 0 && rel < PX) accp[rel] = pk_fma(txd[k], vv, accp[rel]);
+              }
+            }
+            float gxs = 0.f;
+#pragma unroll
+            for (int p = 0; p < PX; ++p) {
+              gB[p] = fmaf(amp, accp[p].x, gB[p]);
+              gxs = fmaf(accp[p].y, tpix[p], gxs);
+            }
+            gxs = wave_sum(gxs);
+            if (lane == 0) REDX[s * C::NW + wid] = gxs;
+          }
         }
         __builtin_amdgcn_s_setprio(0);
       } else {
@@ -957,8 +1060,11 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           bpix[4 * q + 3] = b.w;
         }
       }
-      starlet_l1_grad<N, PX>(bpix, A.W ? A.W + (size_t)f * J * N * N : nullptr, A.norms,
-                             A.qscratch + (size_t)f * J * N * N, A.lam_sc, A.lam_hf, C::WC ? lds + C::OFF_R : lds, tid, l1, z);
+      // (two workgroups, pixel state in registers: role 0 sets the register budget, so role 1 keeps its transpose addresses live)
+      constexpr bool LIVE_ADDR = SPLIT && STATE_REGS && LC_STARLET_LIVE_ADDR;
+      starlet_l1_grad<N, PX, ilog2(N), LIVE_ADDR>(bpix, A.W ? A.W + (size_t)f * J * N * N : nullptr, A.norms,
+                                                  A.qscratch + (size_t)f * J * N * N, A.lam_sc, A.lam_hf,
+                                                  C::WC ? lds + C::OFF_R : lds, tid, l1, z);
     }
     LC_STAMP(42);
     // ---- loss ------------------------------------------------------------------------------

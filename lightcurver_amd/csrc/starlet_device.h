@@ -47,6 +47,11 @@ __device__ __forceinline__ lc_v2f pk_fma(lc_v2f a, lc_v2f b, lc_v2f c) { return 
 #endif
 __device__ __forceinline__ lc_v2f pk_bcast(float v) { return (lc_v2f){v, v}; }
 
+// LC_LAUNDER hides how a value was made, so that what is derived from it is formed again where it is used instead of being
+// formed once and kept live (or spilled).  The PSF kernel launders its thread index once per iteration; the starlet launders
+// its pixel coordinates in front of every transpose, except where the caller has registers to spare and asks for live
+// addresses (starlet_l1_grad_dpp<.., LIVE_ADDR = true>: the two-workgroup PSF kernels with their pixel state in registers,
+// whose register budget is set by the other role).  The one-workgroup form, the joint fit and N = 128 keep the laundered form.
 #ifndef LC_LAUNDER
 #define LC_LAUNDER(x) asm volatile("" : "+v"(x))
 #endif
@@ -664,7 +669,11 @@ __device__ __forceinline__ void line_pass(const float (&own)[PX], const LineLane
 // Starlet l1 value and sub-gradient with every pass in registers: the image alternates between the row-major layout
 // (thread = row pu, samples pv .. pv + PX - 1) and the column-major one (thread = column cv, samples cu0 .. cu0 + PX - 1)
 // through two LDS transposes per scale and direction; weights, coefficients and sub-gradients live in the row-major one.
-template <int N, int PX, int JUSE>
+// LIVE_ADDR: the two LDS offsets of the transposes (rb, cb) and the row offset of the weights are formed once per call and
+// stay in registers through all 4 J transposes; bufA / bufB and the per-pixel steps are then immediates of the LDS instructions.
+// Without it every transpose forms them again from laundered coordinates (two multiplies by the row stride and a dozen adds
+// each), which is what keeps the callers that have no registers to spare from spilling - LC_LAUNDER above.
+template <int N, int PX, int JUSE, bool LIVE_ADDR = false>
 __device__ __forceinline__ void starlet_l1_grad_dpp(const float img[PX], const float *Wf, const float *norms, float *qscr,
                                                     float lam_sc, float lam_hf, float *lds, int tid, float &l1,
                                                     float z[PX]) {
@@ -672,6 +681,8 @@ __device__ __forceinline__ void starlet_l1_grad_dpp(const float img[PX], const f
   float *bufA = lds, *bufB = lds + N * TS;
   const int pu_ = tid / LPR, pv_ = (tid % LPR) * PX;  // row-major: row, first column
   const int cv_ = tid / LPR, cu0_ = (tid % LPR) * PX; // column-major: column, first row
+  const int rb_ = pu_ * TS + pv_, cb_ = cu0_ * TS + cv_;  // (used by the LIVE_ADDR form only, as is wo_)
+  const size_t wo_ = (size_t)pu_ * N + pv_;
   LineLane L;
   L.lil = tid % LPR;
   L.is_first = (L.lil == 0) ? 1.f : 0.f;
@@ -689,13 +700,23 @@ __device__ __forceinline__ void starlet_l1_grad_dpp(const float img[PX], const f
   // only after a barrier that every reader of its previous contents has passed)
   // (a bank swizzle that makes both directions conflict-free was measured on MI355X and not kept: no gain, 6 % slower with one
   //  workgroup per frame - DESIGN.md, "Forms built and removed")
+  auto transpose_offsets = [&](int &rb, int &cb) {
+    if constexpr (LIVE_ADDR) {
+      rb = rb_;
+      cb = cb_;
+    } else {
+      int pu = pu_, pv = pv_, cu0 = cu0_, cv = cv_;
+      LC_LAUNDER(pu);
+      LC_LAUNDER(pv);
+      LC_LAUNDER(cu0);
+      LC_LAUNDER(cv);
+      rb = pu * TS + pv;
+      cb = cu0 * TS + cv;
+    }
+  };
   auto to_columns = [&](const float (&v)[PX], float (&o)[PX]) {
-    int pu = pu_, pv = pv_, cu0 = cu0_, cv = cv_;
-    LC_LAUNDER(pu);
-    LC_LAUNDER(pv);
-    LC_LAUNDER(cu0);
-    LC_LAUNDER(cv);
-    const int rb = pu * TS + pv, cb = cu0 * TS + cv;
+    int rb, cb;
+    transpose_offsets(rb, cb);
 #pragma unroll
     for (int p = 0; p < PX; ++p) bufA[rb + p] = v[p];
     __syncthreads();
@@ -703,12 +724,8 @@ __device__ __forceinline__ void starlet_l1_grad_dpp(const float img[PX], const f
     for (int p = 0; p < PX; ++p) o[p] = bufA[cb + p * TS];
   };
   auto to_rows = [&](const float (&v)[PX], float (&o)[PX]) {
-    int pu = pu_, pv = pv_, cu0 = cu0_, cv = cv_;
-    LC_LAUNDER(pu);
-    LC_LAUNDER(pv);
-    LC_LAUNDER(cu0);
-    LC_LAUNDER(cv);
-    const int rb = pu * TS + pv, cb = cu0 * TS + cv;
+    int rb, cb;
+    transpose_offsets(rb, cb);
 #pragma unroll
     for (int p = 0; p < PX; ++p) bufB[cb + p * TS] = v[p];
     __syncthreads();
@@ -720,10 +737,14 @@ __device__ __forceinline__ void starlet_l1_grad_dpp(const float img[PX], const f
     // weights of this scale: requested before the passes so that the latency hides behind them
     float wj[PX];
     if (Wf) {
-      int pu = pu_, pv = pv_;
-      LC_LAUNDER(pu);
-      LC_LAUNDER(pv);
-      const float4 *wp = (const float4 *)(Wf + (size_t)j * N * N + (size_t)pu * N + pv);
+      size_t wo = wo_;
+      if constexpr (!LIVE_ADDR) {
+        int pu = pu_, pv = pv_;
+        LC_LAUNDER(pu);
+        LC_LAUNDER(pv);
+        wo = (size_t)pu * N + pv;
+      }
+      const float4 *wp = (const float4 *)(Wf + (size_t)j * N * N + wo);
 #pragma unroll
       for (int q = 0; q < PX / 4; ++q) {
         const float4 w4 = wp[q];
@@ -791,13 +812,13 @@ __device__ __forceinline__ void starlet_l1_grad_dpp(const float img[PX], const f
   });
 }
 
-template <int N, int PX, int JUSE = ilog2(N)>
+template <int N, int PX, int JUSE = ilog2(N), bool LIVE_ADDR = false>
 __device__ __forceinline__ void starlet_l1_grad(const float img[PX], const float *Wf, const float *norms, float *qscr,
                                                 float lam_sc, float lam_hf, float *lds, int tid, float &l1,
                                                 float z[PX]) {
   constexpr int LPR = N / PX;
   if constexpr ((LPR == 4 || LPR == 8 || LPR == 16) && PX >= 2 && PX <= 8)  // PX = 16 (1024 threads, 128 registers): the LDS form spills less
-    starlet_l1_grad_dpp<N, PX, JUSE>(img, Wf, norms, qscr, lam_sc, lam_hf, lds, tid, l1, z);
+    starlet_l1_grad_dpp<N, PX, JUSE, LIVE_ADDR>(img, Wf, norms, qscr, lam_sc, lam_hf, lds, tid, l1, z);
   else
     starlet_l1_grad_lds<N, PX, JUSE>(img, Wf, norms, qscr, lam_sc, lam_hf, lds, tid, l1, z);
 }

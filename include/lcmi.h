@@ -216,6 +216,60 @@ int lc_background_frames(lc_ctx *ctx, int K, int h, int w, const float *data, co
 int lc_background_map(lc_ctx *ctx, int K, int h, int w, int bw, int bh, const float *mesh /*[K][ny][nx]*/,
                       float *map /*[K][h][w]*/, float *kernel_ms /*nullable*/);
 
+/* ---- source extraction of whole frames: replaces sep.extract over frames ------------------------------
+ * Reference call sites: lightcurver/processes/star_extraction.py:23 (extract_stars, called at frame_importation.py:130)
+ * and background_estimation.py:32 (the source mask of the two-pass sky).  Detection, 8-connected labelling and
+ * measurement as frozen in DESIGN.md section 5 "Source extraction of frames": sep.extract WITHOUT de-blending and
+ * WITHOUT cleaning (sep's deblend_cont = 1.0, clean = False).
+ *   data [K][h][w]; var [K][h][w] (a variance, not an rms), or NULL and var_scalar [K] one variance per frame.
+ *   A pixel is valid if data and variance are finite and the variance > 0.  filter 1: sep's default 3 x 3 matched
+ *   filter; 0: none.  Detected: snr > thresh.  Objects: the 8-connected components of at least minarea pixels, numbered
+ *   from 1 in the raster order of their first pixels.
+ *   Outputs: objects [K][max_objects] (rows past nobj are zero); nobj [K] the true count; segmap [K][h][w] the object
+ *   number or 0; mask [K][h][w] = segmap > 0; status [K]: 0, 1 = nobj > max_objects (the table holds the first
+ *   max_objects objects, segmap and mask are complete), 2 = an iteration guard of the labelling was reached (no input
+ *   reaches it; the frame's outputs are zero).  The other frames of a call are not affected by a frame's status.
+ *   flag bits: 1 = a bounding-box side > 512 pixels, 2 = a pixel with snr >= 2^16 or not finite (both: x, y, a, b, theta
+ *   are NaN), 4 = the box touches the frame border.
+ * Any h, w >= 1 with h * w < 2^31 (lc_extract_supported, no device needed; LC_ERR_UNSUPPORTED otherwise, and for a K
+ * whose frames do not fit one grid).  LC_ERR_INVALID: K < 1, thresh <= 0 or not finite, minarea < 1, filter not 0 or 1,
+ * max_objects < 1, a missing pointer. */
+typedef struct {
+  float thresh;    /* in units of the pixel's noise; the reference: 3 (catalogue), 2 (source mask) */
+  int32_t minarea; /* the reference: 10 */
+  int32_t filter;  /* 1: sep's default 3 x 3 kernel, 0: filter_kernel=None */
+} lc_extract_cfg;
+typedef struct {
+  int32_t first; /* raster index y * w + x of the object's first pixel */
+  int32_t npix, xmin, xmax, ymin, ymax;
+  int32_t xpeak, ypeak; /* first raster position of the largest snr */
+  int32_t flag, pad;
+  float peak, cpeak; /* largest data value (of the finite ones), largest snr */
+  double x, y, a, b, theta, flux;
+} lc_extract_object; /* 96 bytes */
+int lc_extract_supported(int h, int w);
+int lc_extract_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const float *var /*nullable*/,
+                      const float *var_scalar /*[K], read when var is null*/, const lc_extract_cfg *cfg, int max_objects,
+                      lc_extract_object *objects /*nullable*/, int32_t *nobj /*[K]*/, int32_t *segmap /*nullable*/,
+                      uint8_t *mask /*nullable*/, int32_t *status /*[K]*/, float *kernel_ms /*nullable*/);
+
+/* ---- the arithmetic of importing a frame, with the frame uploaded once -----------------------------------
+ * Reference: lightcurver/processes/frame_importation.py:81-141.  data [K][h][w] in electrons per second, exptime [K].
+ *   1. the sky background as lc_background_frames (bcfg);
+ *   2. if mask_sources_first: lc_extract_frames of sub with the scalar variance globalrms^2 and mcfg (the reference:
+ *      thresh 2, minarea 10, filter 1), then the background again with that mask (background_estimation.py:32-37);
+ *   3. the variance plane in float32 without fused multiply-adds: rt = globalrms t, v = (rt rt + |sub t|) / (t t);
+ *   4. lc_extract_frames of sub with v and ecfg.
+ * Outputs: sub [K][h][w]; mesh_back, mesh_rms [K][ny][nx] (nullable); globalback, globalrms [K]; bg_status [K]
+ * (nullable) as lc_background_frames; objects, nobj, segmap (nullable), ex_status as lc_extract_frames; kernel_ms.
+ * Errors as the two entries it chains; LC_ERR_INVALID also for an exptime that is not finite or <= 0. */
+int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const float *exptime /*[K]*/,
+                     const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg, int mask_sources_first,
+                     const lc_extract_cfg *mcfg /*read when mask_sources_first*/, int max_objects, float *sub,
+                     float *mesh_back /*nullable*/, float *mesh_rms /*nullable*/, float *globalback, float *globalrms,
+                     int32_t *bg_status /*nullable*/, lc_extract_object *objects, int32_t *nobj,
+                     int32_t *segmap /*nullable*/, int32_t *ex_status, float *kernel_ms /*nullable*/);
+
 /* ---- optimiser settings shared by both fits ----------------------------------------------- */
 /* optax.adabelief as driven by STARRED's Optimizer(method='adabelief'):
  * lightcurver/processes/star_photometry.py:113-122, roi_modelling.py:326-334. */

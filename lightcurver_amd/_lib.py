@@ -64,6 +64,21 @@ class BackgroundCfg(C.Structure):
     _fields_ = [('bw', C.c_int32), ('bh', C.c_int32), ('fw', C.c_int32), ('fh', C.c_int32), ('fthresh', C.c_float)]
 
 
+class ExtractCfg(C.Structure):
+    _fields_ = [('thresh', C.c_float), ('minarea', C.c_int32), ('filter', C.c_int32)]
+
+
+class ExtractObject(C.Structure):
+    _fields_ = [('first', C.c_int32), ('npix', C.c_int32), ('xmin', C.c_int32), ('xmax', C.c_int32), ('ymin', C.c_int32),
+                ('ymax', C.c_int32), ('xpeak', C.c_int32), ('ypeak', C.c_int32), ('flag', C.c_int32), ('pad', C.c_int32),
+                ('peak', C.c_float), ('cpeak', C.c_float), ('x', C.c_double), ('y', C.c_double), ('a', C.c_double),
+                ('b', C.c_double), ('theta', C.c_double), ('flux', C.c_double)]
+
+
+# lc_extract_object as a NumPy record: the same 96 bytes
+EXTRACT_OBJECT_DTYPE = np.dtype([(n, {C.c_int32: '<i4', C.c_float: '<f4', C.c_double: '<f8'}[t])
+                                 for n, t in ExtractObject._fields_])
+
 SEGMENT_MAX_OBJECTS = 32   # LC_SEGMENT_MAX_OBJECTS of include/lcmi.h
 
 # every symbol include/lcmi.h declares: name -> (restype, argtypes)
@@ -95,6 +110,12 @@ SIGNATURES = {
     'lc_background_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, C.POINTER(C.c_uint8), C.POINTER(BackgroundCfg), fp,
                                        fp, fp, fp, fp, fp, ip, C.POINTER(C.c_float)]),
     'lc_background_map': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_float)]),
+    'lc_extract_supported': (C.c_int, [C.c_int, C.c_int]),
+    'lc_extract_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(ExtractCfg), C.c_int, vp, ip, ip,
+                                    C.POINTER(C.c_uint8), ip, C.POINTER(C.c_float)]),
+    'lc_import_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(BackgroundCfg), C.POINTER(ExtractCfg),
+                                   C.c_int, C.POINTER(ExtractCfg), C.c_int, fp, fp, fp, fp, fp, ip, vp, ip, ip, ip,
+                                   C.POINTER(C.c_float)]),
     'lc_ctx_stream': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     'lc_ctx_synchronize': (C.c_int, [vp]),
     'lc_timer_start': (C.c_int, [vp]),

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "device_call.h"
+#include "frame_steps.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -587,6 +588,51 @@ static bool bg_batch_fits(int K, const BgGrid &g) {
   return (int64_t)K * g.nx * g.ny < lim && (int64_t)K * bg_map_blocks(g) < lim;
 }
 
+std::vector<double> background_pivots() { return bg_pivots(); }
+
+size_t background_meshes(int h, int w, int bw, int bh) {
+  BgGrid g;
+  return bg_grid(h, w, bw, bh, &g) ? (size_t)g.nx * g.ny : 0;
+}
+
+bool background_batch_fits(int K, int h, int w, int bw, int bh) {
+  BgGrid g;
+  return bg_grid(h, w, bw, bh, &g) && bg_batch_fits(K, g);
+}
+
+hipError_t background_launch(lc_ctx *ctx, int K, int h, int w, const lc_background_cfg *cfg, const BackgroundBuffers &B) {
+  BgGrid g;
+  if (!bg_grid(h, w, cfg->bw, cfg->bh, &g)) return hipErrorInvalidValue;
+  const size_t meshes = (size_t)K * g.nx * g.ny;
+  BgStatArgs S;
+  S.g = g;
+  S.data = B.data;
+  S.mask = B.mask;
+  S.raw_back = B.raw_back;
+  S.raw_rms = B.raw_rms;
+  hipLaunchKernelGGL(bg_stats_kernel, dim3((unsigned)meshes), dim3(kBgStatThreads), 0, ctx->stream, S);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  BgPostArgs P;
+  P.g = g;
+  P.fw = cfg->fw;
+  P.fh = cfg->fh;
+  P.raw_back = B.raw_back;
+  P.raw_rms = B.raw_rms;
+  P.cfac = B.cfac;
+  P.mesh_back = B.mesh_back;
+  P.mesh_rms = B.mesh_rms;
+  P.zy = B.zy;
+  P.globalback = B.globalback;
+  P.globalrms = B.globalrms;
+  P.status = B.status;
+  hipLaunchKernelGGL(bg_post_kernel, dim3((unsigned)K), dim3(kBgThreads), 0, ctx->stream, P);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (B.sub || B.back) e = bg_map_launch(ctx, K, g, B.data, B.mesh_back, B.zy, B.cfac, B.sub, B.back);
+  return e;
+}
+
 }  // namespace lc
 
 using namespace lc;
@@ -637,30 +683,21 @@ int lc_background_frames(lc_ctx *ctx, int K, int h, int w, const float *data, co
   LC_HIP(ctx, call.alloc(meshes, &d_rawr));
   LC_HIP(ctx, call.alloc(meshes, &d_zy));
   LC_HIP(ctx, call.start());
-  BgStatArgs S;
-  S.g = g;
-  S.data = d_data;
-  S.mask = d_mask;
-  S.raw_back = d_rawb;
-  S.raw_rms = d_rawr;
-  hipLaunchKernelGGL(bg_stats_kernel, dim3((unsigned)meshes), dim3(kBgStatThreads), 0, ctx->stream, S);
-  LC_HIP(ctx, hipGetLastError());
-  BgPostArgs P;
-  P.g = g;
-  P.fw = cfg->fw;
-  P.fh = cfg->fh;
-  P.raw_back = d_rawb;
-  P.raw_rms = d_rawr;
-  P.cfac = d_cfac;
-  P.mesh_back = d_mb;
-  P.mesh_rms = d_mr;
-  P.zy = d_zy;
-  P.globalback = d_gb;
-  P.globalrms = d_gr;
-  P.status = d_status;
-  hipLaunchKernelGGL(bg_post_kernel, dim3((unsigned)K), dim3(kBgThreads), 0, ctx->stream, P);
-  LC_HIP(ctx, hipGetLastError());
-  if (d_sub || d_back) LC_HIP(ctx, bg_map_launch(ctx, K, g, d_data, d_mb, d_zy, d_cfac, d_sub, d_back));
+  BackgroundBuffers B;
+  B.data = d_data;
+  B.mask = d_mask;
+  B.cfac = d_cfac;
+  B.sub = d_sub;
+  B.back = d_back;
+  B.mesh_back = d_mb;
+  B.mesh_rms = d_mr;
+  B.globalback = d_gb;
+  B.globalrms = d_gr;
+  B.status = d_status;
+  B.raw_back = d_rawb;
+  B.raw_rms = d_rawr;
+  B.zy = d_zy;
+  LC_HIP(ctx, background_launch(ctx, K, h, w, cfg, B));
   LC_HIP(ctx, call.stop());
   LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;

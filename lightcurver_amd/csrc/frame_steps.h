@@ -1,0 +1,60 @@
+// The whole-frame steps as launches on device pointers: what lc_background_frames (background.hip) and lc_extract_frames
+// (extract.hip) run between their uploads and downloads, so that lc_import_frames can chain them on one uploaded frame.
+// Every function enqueues on ctx->stream and returns without synchronising; the buffers belong to the caller.
+#pragma once
+#include <vector>
+
+#include "device_call.h"
+#include "lc_common.h"
+
+namespace lc {
+
+// ---- sky background (background.hip) -----------------------------------------------------------------------------
+
+struct BackgroundBuffers {
+  const float *data = nullptr;      // [K][h][w]
+  const uint8_t *mask = nullptr;    // [K][h][w], nullable
+  const double *cfac = nullptr;     // background_pivots()
+  float *sub = nullptr, *back = nullptr;            // [K][h][w], nullable
+  float *mesh_back = nullptr, *mesh_rms = nullptr;  // [K][ny][nx]
+  float *globalback = nullptr, *globalrms = nullptr;  // [K]
+  int32_t *status = nullptr;                          // [K], nullable
+  float *raw_back = nullptr, *raw_rms = nullptr, *zy = nullptr;  // [K][ny][nx] scratch
+};
+
+// the pivots of the splines' Thomas sweep, the same for every call
+std::vector<double> background_pivots();
+// meshes of one frame, 0 if (h, w, bw, bh) is no grid
+size_t background_meshes(int h, int w, int bw, int bh);
+// K frames go into one grid (lc_background_supported answers for the frame alone)
+bool background_batch_fits(int K, int h, int w, int bw, int bh);
+// the three launches of lc_background_frames; the arguments have been checked
+hipError_t background_launch(lc_ctx *ctx, int K, int h, int w, const lc_background_cfg *cfg, const BackgroundBuffers &B);
+
+// ---- source extraction (extract.hip) -----------------------------------------------------------------------------
+
+struct ExtractBuffers {
+  const float *data = nullptr;        // [K][h][w]
+  const float *var = nullptr;         // [K][h][w], or null:
+  const float *var_scalar = nullptr;  // [K]
+  lc_extract_object *objects = nullptr;  // [K][max_objects], nullable
+  int32_t *nobj = nullptr;               // [K]
+  int32_t *segmap = nullptr;             // [K][h][w], nullable
+  uint8_t *mask = nullptr;               // [K][h][w], nullable
+  int32_t *status = nullptr;             // [K]
+  // scratch: extract_scratch() fills these
+  float *snr = nullptr;                          // [K][h][w]
+  int32_t *label = nullptr, *count = nullptr;    // [K][h][w]
+  int32_t *block = nullptr;                      // [K][blocks of 256 pixels]
+  int32_t *aux = nullptr;                        // [K][max_objects][6]: first, npix, xmin, xmax, ymin, ymax
+};
+
+// K frames of h x w go into the grids of the extraction
+bool extract_batch_fits(int K, int h, int w);
+// allocates the scratch buffers of one extraction from the call's pool (aux only with objects)
+hipError_t extract_scratch(DeviceCall &call, int K, int h, int w, int max_objects, bool with_objects, ExtractBuffers *B);
+// every launch of lc_extract_frames; the arguments have been checked
+hipError_t extract_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg *cfg, int max_objects,
+                          const ExtractBuffers &B);
+
+}  // namespace lc

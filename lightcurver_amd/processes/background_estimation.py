@@ -1,9 +1,13 @@
 """The reference's ``subtract_background`` (lightcurver/processes/background_estimation.py:5-39, called once per frame at
 frame_importation.py:81-91) on the device: the sky model of ``lightcurver_amd.sep.Background``, its subtraction and
-``bkg.globalrms`` in one call per frame, or one call per frame shape for a whole list of frames."""
+``bkg.globalrms`` in one call per frame, or one call per frame shape for a whole list of frames.  The reference's two-pass
+form (``mask_sources_first=True``: sky, sources of the subtracted frame, sky again without them) is
+``subtract_background_masking_sources``."""
 import numpy as np
 
 from .. import sep
+
+MASK_THRESH, MASK_MINAREA = 2, 10          # the reference's sep.extract of the source mask (background_estimation.py:32-33)
 
 
 def _box_size(shape, n_boxes):
@@ -54,3 +58,28 @@ def subtract_background_batch(images, masks=None, n_boxes=10, ctx=None):
         for i, si, bi in zip(idx, s, b):
             subs[i], bkgs[i] = si, bi
     return subs, bkgs
+
+
+def subtract_background_masking_sources_batch(images, n_boxes=10, thresh=MASK_THRESH, minarea=MASK_MINAREA, ctx=None):
+    """The reference's ``subtract_background(image, mask_sources_first=True)`` for a (K, h, w) stack: the sky, the
+    sources of the subtracted frames above ``thresh`` sigma of the frame's ``globalrms`` (at least ``minarea`` pixels,
+    ``sep.extract_frames``), and the sky again with those sources masked.  Returns (list of image_sub, list of bkg,
+    masks uint8 (K, h, w))."""
+    images = np.asarray(images)
+    if images.ndim != 3:
+        raise ValueError(f'expected a (K, h, w) stack of frames, got {images.shape}')
+    box = _box_size(images.shape, n_boxes)
+    first = sep.background_frames(images, None, bw=box, bh=box, fw=3, fh=3, sub=True, back=False, ctx=ctx)
+    rms = first['globalrms'].astype(np.float32)
+    found = sep.extract_frames(first['sub'], rms * rms, thresh, minarea, objects=False, mask=True, ctx=ctx)
+    subs, bkgs = _stack(images, found['mask'], n_boxes, ctx)
+    return list(subs), bkgs, found['mask']
+
+
+def subtract_background_masking_sources(image, n_boxes=10, thresh=MASK_THRESH, minarea=MASK_MINAREA, ctx=None):
+    """The same for one 2-D frame: returns (image_sub, bkg) as the reference does."""
+    image = np.asarray(image)
+    if image.ndim != 2:
+        raise ValueError(f'subtract_background_masking_sources takes one 2-D frame, got {image.shape}')
+    subs, bkgs, _ = subtract_background_masking_sources_batch(image[None], n_boxes, thresh, minarea, ctx)
+    return subs[0], bkgs[0]

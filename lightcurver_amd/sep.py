@@ -1,11 +1,16 @@
-"""``Background`` with sep's signature, on the device (``lc_background_frames``, include/lcmi.h).
+"""``Background`` and ``extract`` with sep's signatures, on the device (``lc_background_frames``, ``lc_extract_frames``,
+include/lcmi.h).
 
 The reference estimates the sky of every frame it imports with ``sep.Background(image, bw=box, bh=box, fw=3, fh=3)``,
 subtracts it (``image - bkg``) and keeps ``bkg.globalrms`` for the noise maps of the stamps
 (lightcurver/processes/background_estimation.py:25, frame_importation.py:81-91).  Here the SPEC of DESIGN.md §5 ("Sky
 background") runs as HIP kernels over whole frames: a 2-D input is one frame, a (K, h, w) stack is one batched call
 whose ``globalback`` and ``globalrms`` are arrays of K.  Only ``fw = fh`` of 1 or 3 with ``fthresh = 0`` is built (the
-reference uses 3); anything else raises ``NotImplementedError``.  There is no CPU fallback."""
+reference uses 3); anything else raises ``NotImplementedError``.
+
+``extract`` is the SPEC "Source extraction of frames" of the same section: detection, 8-connected labelling and
+measurement of whole frames, that is ``sep.extract`` WITHOUT de-blending and WITHOUT cleaning.  There is no CPU
+fallback."""
 import ctypes as C
 
 import numpy as np
@@ -139,3 +144,139 @@ class Background:
         time): for a float32 image the same bits as the ``sub`` of lc_background_frames.  One call for both is
         ``processes.background_estimation.subtract_background``, which takes the fused ``sub``."""
         return np.asarray(other) - self.back()
+
+
+# ---- source extraction ---------------------------------------------------------------------------------------------
+
+DEFAULT_FILTER_KERNEL = np.array([[1., 2., 1.], [2., 4., 2.], [1., 2., 1.]])       # sep's default
+OBJECT_FIELDS = ('x', 'y', 'a', 'b', 'theta', 'flux', 'npix', 'peak', 'cpeak', 'xmin', 'xmax', 'ymin', 'ymax', 'xpeak',
+                 'ypeak', 'flag')
+OBJECT_DTYPE = np.dtype([(n, _lib.EXTRACT_OBJECT_DTYPE[n]) for n in OBJECT_FIELDS])
+FLAG_LARGE, FLAG_RANGE, FLAG_EDGE = 1, 2, 4
+_DEFAULT = object()
+
+
+def extract_supported(h, w):
+    """True if the kernels take (h, w) frames (no device needed): h, w >= 1 and h w < 2^31."""
+    return bool(_lib.lib().lc_extract_supported(int(h), int(w)))
+
+
+def _filter_flag(filter_kernel):
+    if filter_kernel is None:
+        return 0
+    if filter_kernel is _DEFAULT:
+        return 1
+    k = np.asarray(filter_kernel, dtype=np.float64)
+    if k.shape == (3, 3) and np.array_equal(k, DEFAULT_FILTER_KERNEL):
+        return 1
+    raise NotImplementedError("extract: only sep's default 3 x 3 filter_kernel and None are built")
+
+
+def extract_cfg(thresh, minarea, filter_kernel=_DEFAULT):
+    if not np.isfinite(thresh) or not thresh > 0:
+        raise ValueError(f'extract: thresh = {thresh} must be finite and > 0')
+    if int(minarea) < 1:
+        raise ValueError(f'extract: minarea = {minarea}')
+    return _lib.ExtractCfg(float(thresh), int(minarea), _filter_flag(filter_kernel))
+
+
+def extract_frames(stack, var, thresh, minarea=5, filter_kernel=_DEFAULT, max_objects=8192, segmentation_map=False,
+                   mask=False, objects=True, ctx=None):
+    """One device call over a (K, h, w) stack.  ``var``: a (K, h, w) stack of variances, or one variance per frame
+    (a scalar or K of them).  Returns dict(objects: list of K record arrays of lc_extract_object (all its fields; None
+    without ``objects``), nobj, status int32 (K,): 0, 1 = more objects than ``max_objects`` (the call is repeated once
+    with the largest nobj, so 1 is not seen from here), 2 = the labelling's guard, segmap int32 (K, h, w) and mask uint8
+    where asked for, kernel_ms)."""
+    d = f32(stack)
+    if d.ndim != 3:
+        raise ValueError(f'expected a (K, h, w) stack of frames, got {d.shape}')
+    K, h, w = d.shape
+    cfg = extract_cfg(thresh, minarea, filter_kernel)
+    if h < 1 or w < 1:
+        raise ValueError(f'extract: frames of {h} x {w} pixels')
+    if not extract_supported(h, w):
+        raise NotImplementedError(f'extract: {h} x {w} pixels is 2^31 or more')
+    if int(max_objects) < 1:
+        raise ValueError(f'extract: max_objects = {max_objects}')
+    v = f32(var)
+    if v.ndim == 3:
+        if v.shape != d.shape:
+            raise ValueError('var must have the shape of the data, or be one value per frame')
+        vplane, vscalar = v, None
+    else:
+        vplane, vscalar = None, np.ascontiguousarray(np.broadcast_to(v.reshape(-1), (K,)), dtype=np.float32)
+    ctx = ctx or _lib.default_context()
+    out = dict(nobj=np.zeros(K, np.int32), status=np.zeros(K, np.int32), objects=None,
+               segmap=np.zeros(d.shape, np.int32) if segmentation_map else None,
+               mask=np.zeros(d.shape, np.uint8) if mask else None, kernel_ms=0.0)
+    if not K:
+        out['objects'] = [] if objects else None
+        return out
+    cap = int(max_objects)
+    for attempt in range(2):
+        table = np.zeros((K, cap), _lib.EXTRACT_OBJECT_DTYPE) if objects else None
+        ms = C.c_float()
+        ctx.check(_lib.lib().lc_extract_frames(
+            ctx.h, K, h, w, ptr(d), ptr(vplane), ptr(vscalar), C.byref(cfg), cap,
+            table.ctypes.data_as(C.c_void_p) if objects else None, out['nobj'].ctypes.data_as(_i32p),
+            out['segmap'].ctypes.data_as(_i32p) if segmentation_map else None,
+            out['mask'].ctypes.data_as(_u8p) if mask else None, out['status'].ctypes.data_as(_i32p), C.byref(ms)),
+            'lc_extract_frames')
+        out['kernel_ms'] += ms.value
+        if not objects or not (out['status'] == 1).any():
+            break
+        cap = int(out['nobj'].max())          # the true counts: the second call holds them all
+    if objects:
+        out['objects'] = [table[k, :min(int(out['nobj'][k]), cap)].copy() for k in range(K)]
+    return out
+
+
+def extract(data, thresh, err=None, var=None, mask=None, minarea=5, filter_kernel=_DEFAULT, deblend_cont=1.0, clean=False,
+            segmentation_map=False, max_objects=65536, ctx=None):
+    """``sep.extract`` of one frame, without de-blending and without cleaning: note that sep's own defaults are
+    ``deblend_cont=0.005`` and ``clean=True``, which are not built, so those two arguments default to what is
+    (``deblend_cont=1.0``, ``clean=False``) and anything else raises ``NotImplementedError``, as does a ``filter_kernel``
+    other than ``None`` or sep's default 3 x 3 one.  ``thresh`` is in units of the pixel's noise: ``err`` (an rms) or
+    ``var`` (a variance), a scalar or an array; without either the variance is 1.  ``mask``: non-zero pixels are invalid.
+    Returns a structured array with sep's field names for what is measured (x, y, a, b, theta, flux, npix, peak, cpeak,
+    xmin, xmax, ymin, ymax, xpeak, ypeak, flag), and with ``segmentation_map=True`` also the int32 map.  A blended pair
+    comes out as one elongated object."""
+    if float(deblend_cont) != 1.0:
+        raise NotImplementedError('extract: de-blending is not built; pass deblend_cont=1.0 (sep\'s default is 0.005)')
+    if clean:
+        raise NotImplementedError('extract: cleaning is not built; pass clean=False (sep\'s default is True)')
+    _filter_flag(filter_kernel)
+    d = f32(data)
+    if d.ndim != 2:
+        raise ValueError(f'extract takes one 2-D frame, got {d.shape}')
+    if err is not None and var is not None:
+        raise ValueError('extract: err and var are exclusive')
+    if err is not None:
+        e = np.asarray(err, dtype=np.float32)
+        v = e * e                             # in float32, as the SPEC says of a caller with err
+    elif var is not None:
+        v = np.asarray(var, dtype=np.float32)
+    else:
+        v = np.float32(1.0)
+    v = np.asarray(v, np.float32)
+    if v.ndim not in (0, 2) or (v.ndim == 2 and v.shape != d.shape):
+        raise ValueError('extract: err / var must be a scalar or have the shape of the data')
+    if mask is not None:
+        m = np.asarray(mask) != 0
+        if m.shape != d.shape:
+            raise ValueError('mask must have the shape of the data')
+        v = np.where(m, np.float32(np.nan), np.broadcast_to(v, d.shape)).astype(np.float32)
+    r = extract_frames(d[None], v[None] if v.ndim == 2 else v, thresh, minarea, filter_kernel, max_objects,
+                       segmentation_map=segmentation_map, ctx=ctx)
+    if int(r['status'][0]) == 2:
+        raise _lib.LcError('extract: the iteration guard of the labelling was reached')
+    objects = objects_view(r['objects'][0])
+    return (objects, r['segmap'][0]) if segmentation_map else objects
+
+
+def objects_view(table):
+    """The record array of lc_extract_object as a structured array with sep's field names, in their order."""
+    out = np.zeros(len(table), OBJECT_DTYPE)
+    for n in OBJECT_FIELDS:
+        out[n] = table[n]
+    return out

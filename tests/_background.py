@@ -342,3 +342,33 @@ def precision_figures():
         m32, m64 = spline_map(mesh, h, w, box, box, np.float32), spline_map(mesh, h, w, box, box, np.float64)
         fig['map'] = max(fig['map'], float(np.abs(m32 - m64).max() / np.abs(mesh).max()))
     return fig
+
+
+# (h, w, bw, bh, nstars, seed, K, (ny, nx)): meshes whose sides differ, on scene(h, w, nstars, seed + k).  A kernel that
+# swapped the two sides, or used one of them for both, gives another grid (tests/test_background_cpu.py asserts that the
+# three wrong grids differ from the right one, and that the swapped restatement is far outside the device bounds).
+UNEQUAL_CASES = (
+    (67, 45, 8, 5, 6, 6, 2, (14, 6)),
+    (130, 195, 13, 65, 40, 3, 1, (2, 15)),
+    (130, 195, 65, 13, 40, 3, 1, (10, 3)),
+    (48, 80, 16, 80, 4, 2, 1, (1, 5)),              # a single mesh row
+    (48, 80, 48, 10, 4, 2, 1, (5, 2)),
+)
+_unequal_wanted = {}
+
+
+def unequal_wanted(case):
+    """(frames (K, h, w), [the restatement of each frame, without maps]) of one UNEQUAL_CASES entry, computed once and
+    shared by the CPU and the device tests."""
+    if case not in _unequal_wanted:
+        h, w, bw, bh, nstars, seed, K, _ = case
+        frames = np.stack([scene(h, w, nstars, seed + k) for k in range(K)])
+        _unequal_wanted[case] = frames, [background(f, bw=bw, bh=bh, maps=False) for f in frames]
+    return _unequal_wanted[case]
+
+
+def unequal_mask(h, w):
+    """The mask of the masked case: a block that covers whole meshes of 13 x 65 and 65 x 13 pixels, and scattered pixels."""
+    m = np.random.default_rng(h + w).random((h, w)) < 0.02
+    m[:65, :39] = True
+    return m

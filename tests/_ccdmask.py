@@ -145,3 +145,28 @@ def quantised_stamp(n):
     q[n // 2, 1] = 4.0
     q[n // 2 + 3, 1] = 4.0          # three lines below the other one in the same column: step 5 fills the gap
     return q
+
+
+# ---- settings other than the defaults --------------------------------------------------------------------------------
+SETTINGS_SIZES = ((16, 16), (33, 12))          # (n, K) of device_batch(n, K, seed=n)
+
+
+def settings_cases(n):
+    """The settings of the device comparison at stamp size n, each a dict of what differs from lsigma = hsigma = 9,
+    ngood = 5.  Every one changes the restatement's ``mask`` on device_batch(n, K, seed=n) (asserted by
+    tests/test_ccdmask_cpu.py).  The asymmetric pair catches a swap of the two thresholds; ngood = n - 2 is the last
+    value at which the fill loop runs, and there it reads the last row; from n - 1 on no line can start a fill."""
+    return ([dict(lsigma=3), dict(hsigma=3), dict(lsigma=3, hsigma=20), dict(lsigma=0)]
+            + [dict(ngood=g) for g in (0, 1, 2, n - 3, n - 2, n - 1, n, n + 5)] + [dict(lsigma=2, hsigma=2, ngood=n - 2)])
+
+
+_settings_wanted = {}
+
+
+def settings_wanted(n, K):
+    """(data, the restatement at the defaults, [(settings, the restatement with them)]) of one SETTINGS_SIZES entry,
+    computed once and shared by the CPU and the device tests."""
+    if (n, K) not in _settings_wanted:
+        d = device_batch(n, K, seed=n)
+        _settings_wanted[n, K] = d, ccdmask(d), [(kw, ccdmask(d, **kw)) for kw in settings_cases(n)]
+    return _settings_wanted[n, K]

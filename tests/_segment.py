@@ -310,3 +310,72 @@ def crowded_stamp(n=64, blob=5, pitch=9, seed=0):
             model[y:y + blob, x:x + blob] = 40.0 + 3.0 * rng.uniform()
     data = model + 0.3 * rng.standard_normal((n, n))
     return data.astype(F32), np.ones((n, n), F32)
+
+
+# ---- settings other than the defaults --------------------------------------------------------------------------------
+SETTINGS_SIZES = ((24, 24), (33, 12))          # (n, K) of make_scenes(K, n, seed=100 n + K) and make_pairs(K, n, the same)
+# (what differs from thresh 3, minarea 15, deblend_nthresh 32, deblend_cont 0.001, clean on; the settings it is
+# compared with beyond those defaults; the input; the sizes it runs at).  A case exists to catch a kernel that ignores or
+# mis-uses that setting, so the restatement's segmap with it must differ from the one at its base, and from the one
+# at the defaults (tests/test_segment_cpu.py asserts both for every entry).  On the scenes deblend_cont 0.05 and 1e-6
+# change nothing, so they run on make_pairs.  Cleaning merges every fragment of a share below 0.001 into the primary
+# (whose wing at a distance d is about 3 npix / (pi d^2) above the threshold, more than such a fragment's pixels), so
+# 1e-6 is told apart from 0.001 with cleaning off only.
+SETTINGS = (
+    (dict(thresh=1.5), {}, 'scenes', (24, 33)),
+    (dict(thresh=6.0), {}, 'scenes', (24, 33)),
+    (dict(minarea=1), {}, 'scenes', (24, 33)),
+    (dict(minarea=5), {}, 'scenes', (24, 33)),
+    (dict(minarea=40), {}, 'scenes', (24,)),
+    (dict(deblend_cont=1.0), {}, 'scenes', (24, 33)),
+    (dict(clean=False), {}, 'scenes', (24, 33)),
+    (dict(thresh=1.5, minarea=3, deblend_cont=1e-5), {}, 'scenes', (24, 33)),
+    (dict(deblend_nthresh=4), {}, 'scenes', (24, 33)),
+    (dict(deblend_nthresh=8), {}, 'scenes', (24, 33)),
+    (dict(deblend_nthresh=16), {}, 'scenes', (24, 33)),
+    (dict(deblend_cont=0.05), {}, 'pairs', (24, 33)),
+    (dict(deblend_cont=1e-6), dict(clean=False), 'pairs', (24, 33)),
+)
+
+
+def make_pairs(K, n, seed):
+    """K blended pairs for deblend_cont, float32 (data, noisemap) (K, n, n), with the noise model of make_scene.  Even
+    stamps: a secondary of about 1 % of the pair's flux, which 0.05 merges and 0.001 splits.  Odd stamps: a faint wide
+    secondary on the rim of the primary's group, its share between 1e-6 and 1e-3, the noise drawn at a tenth of the
+    noise map so that the share is the designed one."""
+    rng = np.random.default_rng(seed)
+    u = n / 32.0
+    c = (n - 1) / 2.0
+    s = max(1.0, 1.8 * u)
+    share = ((1000.0, 20.0, 10.0), (1000.0, 80.0, 8.0), (3000.0, 40.0, 10.0), (3000.0, 300.0, 8.0))
+    datas, noises = [], []
+    for k in range(K):
+        jx, jy = rng.uniform(-0.5, 0.5, 2)
+        ang = rng.uniform(0.0, 2.0 * np.pi)
+        amp1, amp2, sep, s2, level = (share[k // 2 % 4] + (s, 1.0)) if k % 2 == 0 else (1000.0, 2.0, 10.0, 1.2 * s, 0.1)
+        model = _star(n, c + jx, c + jy, amp1, s)
+        model += _star(n, c + jx + sep * u * np.cos(ang), c + jy + sep * u * np.sin(ang), amp2, s2)
+        noise = np.sqrt(1.0 + model / 4.0)
+        datas.append(model + level * noise * rng.standard_normal((n, n)))
+        noises.append(noise)
+    return np.stack(datas).astype(F32), np.stack(noises).astype(F32)
+
+
+_settings_wanted = {}
+
+
+def settings_wanted(n, K):
+    """[(settings of the case, data, noisemap, the restatement with them, at their base, at the defaults)] of one
+    SETTINGS_SIZES entry, computed once and shared by the CPU and the device tests."""
+    if (n, K) not in _settings_wanted:
+        d, s, _ = make_scenes(K, n, seed=100 * n + K)
+        inputs = dict(scenes=(d, s), pairs=make_pairs(K, n, seed=100 * n + K))
+        plain = {name: segment(*pair) for name, pair in inputs.items()}
+        out = []
+        for changed, base, name, sizes in SETTINGS:
+            if n in sizes:
+                d, s = inputs[name]
+                out.append((dict(base, **changed), d, s, segment(d, s, **dict(base, **changed)),
+                            segment(d, s, **base) if base else plain[name], plain[name]))
+        _settings_wanted[n, K] = out
+    return _settings_wanted[n, K]

@@ -90,6 +90,40 @@ def test_stack_restatement_equals_the_host_function(case):
     assert np.nanmax(np.abs(plain['stack'] - mean)) <= 1e-12 * np.nanmax(np.abs(mean))
 
 
+@pytest.mark.parametrize('case,n_sigma', AS.N_SIGMA_CASES)
+def test_stack_restatement_at_other_n_sigma(case, n_sigma):
+    """The figure the device is held to four times of at an n_sigma other than 3 (AS.F32_STACK_ERROR_N_SIGMA,
+    DESIGN.md): printed, and not exceeded.  The case is there to catch a kernel that ignores n_sigma, so the rejection
+    counts must differ from those at n_sigma = 3, and few pixels may sit on a rejection boundary."""
+    E, n = case
+    values, noise, o64, o32, at3 = AS.n_sigma_wanted(case, n_sigma)
+    near = o64['near']
+    assert near.mean() <= AS.NEAR_CAP
+    differ = (o64['n_rejected'] != at3['n_rejected']).mean()
+    assert differ >= 0.05 and not np.array_equal(o64['stack'], at3['stack'], equal_nan=True)
+    ok = ~near
+    assert np.array_equal(o32['n_rejected'][ok], o64['n_rejected'][ok])
+    assert np.array_equal(np.isnan(o32['stack']), np.isnan(o64['stack']))
+    err = np.nanmax(np.abs(o32['stack'][ok] - o64['stack'][ok])) / np.nanmax(np.abs(o64['stack']))
+    recorded = AS.F32_STACK_ERROR_N_SIGMA[case, n_sigma]
+    print(f'E={E} n={n} n_sigma={n_sigma}: near a boundary {near.mean():.4f}, rejected epochs per pixel '
+          f'{o64["n_rejected"].mean():.2f} ({at3["n_rejected"].mean():.2f} at 3; {differ:.2f} of the pixels differ), float32 '
+          f'stack {err:.2e} (recorded {recorded:.1e})')
+    assert err <= recorded
+    # the sigma-clipped stack of the host function at this n_sigma, up to the order of its sums
+    from lightcurver_amd.processes.roi_modelling import sigma_clipped_weighted_stack
+    host = sigma_clipped_weighted_stack(values[0], noise, n_sigma=n_sigma)
+    assert np.nanmax(np.abs(host - o64['stack'][0])) <= 1e-12 * np.nanmax(np.abs(host))
+
+
+def test_n_sigma_cases_are_the_listed_ones():
+    assert set(AS.F32_STACK_ERROR_N_SIGMA) == set(AS.N_SIGMA_CASES) and len(AS.N_SIGMA_CASES) == 10
+    assert all(ns != 3.0 and tuple(case) in AS.STACK_CASES for case, ns in AS.N_SIGMA_CASES)
+    # (3, 16) at n_sigma 1: the float64 restatement alone has more pixels on a boundary than the cap allows
+    values, noise = AS.make_stack_case(3, 3, 16, AS.stack_seed((3, 16)))
+    assert AS.stack_cubes(values, noise, n_sigma=1.0)['near'].mean() > AS.NEAR_CAP
+
+
 def test_symbols_are_exported_and_the_size_query_needs_no_device():
     from lightcurver_amd import _lib
     handle = ctypes.CDLL(_lib.LIB_PATH)

@@ -98,6 +98,29 @@ def test_stack_stage_equals_the_restatement(ctx, case):
     assert np.nanmax(np.abs(plain['stack'] - p64['stack'])) <= 4 * AS.F32_STACK_ERROR[case] * np.nanmax(np.abs(p64['stack']))
 
 
+@pytest.mark.parametrize('case,n_sigma', AS.N_SIGMA_CASES)
+def test_stack_stage_at_other_n_sigma(ctx, case, n_sigma):
+    """The assertions of test_stack_stage_equals_the_restatement at an n_sigma other than 3, where the rejection counts
+    differ from those at 3 (tests/test_align_stack_cpu.py asserts that), against four times the figure measured for this
+    (case, n_sigma)."""
+    from lightcurver_amd.processes.roi_modelling import align_stack_batch
+    E, n = case
+    values, noise, o64, o32, at3 = AS.n_sigma_wanted(case, n_sigma)
+    got = align_stack_batch(values, noise, n_sigma=n_sigma, want=('stack', 'median', 'n_rejected'), ctx=ctx)
+    assert np.array_equal(_bits(got['median']), _bits(o32['median']))
+    near = o64['near']
+    assert near.mean() <= AS.NEAR_CAP
+    ok = ~near
+    bound = 4 * AS.F32_STACK_ERROR_N_SIGMA[case, n_sigma]
+    err = np.nanmax(np.abs(got['stack'][ok] - o64['stack'][ok])) / np.nanmax(np.abs(o64['stack']))
+    print(f'E={E} n={n} n_sigma={n_sigma}: device stack against float64 {err:.2e} (bound {bound:.1e}), rejected epochs per '
+          f'pixel {got["n_rejected"].mean():.2f} (restatement {o64["n_rejected"].mean():.2f}, at 3 '
+          f'{at3["n_rejected"].mean():.2f}), left out {near.sum()} pixels')
+    assert got['n_rejected'].dtype == np.int32 and np.array_equal(got['n_rejected'][ok], o64['n_rejected'][ok])
+    assert np.array_equal(np.isnan(got['stack'][ok]), np.isnan(o64['stack'][ok]))
+    assert err <= bound
+
+
 def test_stack_data_diagnostic_on_device_equals_the_host(ctx):
     from lightcurver_amd.processes import roi_modelling as RM
     from lightcurver_amd.starred.deconvolution.deconvolution import setup_model

@@ -186,6 +186,35 @@ def test_bad_meshes_take_the_nearest_good_ones():
     assert np.array_equal(fr, fb * 2)
 
 
+@pytest.mark.parametrize('case', B.UNEQUAL_CASES)
+def test_unequal_mesh_sides_cannot_be_swapped_unnoticed(case):
+    """The condition of B.UNEQUAL_CASES: with the sides swapped, or one side used for both, the grid has another shape,
+    and the swapped restatement's globalback is far outside four times the precision figure, the device's bound."""
+    h, w, bw, bh, nstars, seed, K, shape = case
+    assert bw != bh and B.grid(h, w, bw, bh) == shape
+    assert len({shape, B.grid(h, w, bh, bw), B.grid(h, w, bw, bw), B.grid(h, w, bh, bh)}) == 4
+    frames, wants = B.unequal_wanted(case)
+    assert frames.shape == (K, h, w)
+    bound = 4.0 * B.precision_figures()['mesh_back']
+    for frame, want in zip(frames, wants):
+        assert want['status'] == 0 and want['mesh_back'].shape == shape and want['mesh_rms'].shape == shape
+        swapped = B.background(frame, bw=bh, bh=bw, maps=False)
+        off = abs(float(swapped['globalback']) - float(want['globalback'])) / float(want['globalrms'])
+        print(f'{h} x {w} in {bw} x {bh}: grid {shape}, swapped {swapped["mesh_back"].shape}; globalback '
+              f'{want["globalback"]:.4f}, swapped {swapped["globalback"]:.4f}: {off:.3g} of globalrms (the device bound '
+              f'{bound:.3g})')
+        assert off > 10 * bound
+        # the map through these mesh values: against scipy's spline with the nodes of these sides
+        got = B.spline_map(want['mesh_back'], h, w, bw, bh, np.float64)
+        ref = _scipy_map(want['mesh_back'].astype(np.float64), h, w, bw, bh)
+        assert np.abs(got - ref).max() < 1e-11 * np.abs(want['mesh_back']).max()
+    p = wants[0]['paths']
+    assert p['single_y'] == (shape[0] == 1) and not p['single_x']
+    if (bw, bh) in ((13, 65), (65, 13)):
+        r = B.background(frames[0], mask=B.unequal_mask(h, w), bw=bw, bh=bh, maps=False)
+        assert r['status'] == 0 and r['paths']['bad'] >= 3 and r['paths']['filled'] == r['paths']['bad']
+
+
 def test_precision_figures():
     """Float32 steps against all-float64 over the test scenes, in units of each frame's globalrms: the figures of the
     DESIGN.md section, and four times them the parity bounds of the device tests."""

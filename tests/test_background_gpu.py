@@ -1,5 +1,5 @@
 """GPU parity of the sky background of whole frames (lc_background_frames, lc_background_map; DESIGN.md §5 "Sky
-background") against the NumPy restatement of the SPEC (tests/_background.py).
+background") against the NumPy restatement of the SPEC (tests/_background.py), with square meshes and with bw != bh.
 
 Bounds.  Mesh values and global values: 4 x the float32-against-float64 figure of the restatement over the test scenes
 (``_background.precision_figures``, measured again here, not a number written down), in units of the frame's globalrms:
@@ -19,19 +19,25 @@ _u8p = C.POINTER(C.c_uint8)
 _i32p = C.POINTER(C.c_int32)
 
 
+def _sides(box):
+    return tuple(box) if isinstance(box, tuple) else (box, box)
+
+
 def _call(ctx, frames, box, mask=None, fw=3, want=('sub', 'back', 'mesh_back', 'mesh_rms', 'status')):
-    """lc_background_frames through ctypes, with the outputs of ``want`` and null pointers for the others."""
+    """lc_background_frames through ctypes, with the outputs of ``want`` and null pointers for the others.  box: the
+    side of square meshes, or (bw, bh)."""
     from lightcurver_amd import _lib
     d = _lib.f32(frames)
     K, h, w = d.shape
-    ny, nx = B.grid(h, w, box, box)
+    bw, bh = _sides(box)
+    ny, nx = B.grid(h, w, bw, bh)
     out = dict(sub=np.full(d.shape, -7.0, np.float32), back=np.full(d.shape, -7.0, np.float32),
                mesh_back=np.full((K, ny, nx), -7.0, np.float32), mesh_rms=np.full((K, ny, nx), -7.0, np.float32),
                status=np.full(K, 99, np.int32))
     out = {k: v for k, v in out.items() if k in want}
     gb, gr = np.empty(K, np.float32), np.empty(K, np.float32)
     m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-    cfg = _lib.BackgroundCfg(box, box, fw, fw, 0.0)
+    cfg = _lib.BackgroundCfg(bw, bh, fw, fw, 0.0)
     ms = C.c_float()
     st = out.get('status')
     ctx.check(_lib.lib().lc_background_frames(
@@ -70,7 +76,7 @@ def _check_map(got, k, frame, box, what=''):
     """back and sub of frame k against the float64 spline through the device's own mesh values."""
     h, w = frame.shape
     mesh = got['mesh_back'][k]
-    want = B.spline_map(mesh, h, w, box, box, np.float64)
+    want = B.spline_map(mesh, h, w, *_sides(box), np.float64)
     scale = np.abs(mesh).max()
     err = np.abs(got['back'][k] - want).max()
     print(f'{what} frame {k}: map {err / max(scale, 1e-300):.3g} of the largest mesh value')
@@ -122,6 +128,54 @@ def test_parity_with_the_restatement(ctx, bounds, h, w, box, K, nstars, seed, pa
         one = _call(ctx, frames[k:k + 1], box)
         for key in ('sub', 'back', 'mesh_back', 'mesh_rms', 'globalback', 'globalrms', 'status'):
             assert np.array_equal(one[key][0], got[key][k]), key
+
+
+@pytest.mark.parametrize('case', B.UNEQUAL_CASES)
+def test_unequal_mesh_sides(ctx, bounds, case):
+    """bw != bh through lc_background_frames, lc_background_map alone and the sep mirror.  With the sides swapped, or one
+    used for both, the grid has another shape and the global values are far outside the bounds
+    (tests/test_background_cpu.py asserts that), so a kernel that did either fails here."""
+    from lightcurver_amd import sep
+    h, w, bw, bh, nstars, seed, K, shape = case
+    frames, wants = B.unequal_wanted(case)
+    got = _call(ctx, frames, (bw, bh))
+    assert got['mesh_back'].shape == got['mesh_rms'].shape == (K,) + shape
+    for k in range(K):
+        _check_meshes(got, k, wants[k], bounds, f'{h} x {w} in {bw} x {bh}')
+        _check_map(got, k, frames[k], (bw, bh), f'{h} x {w} in {bw} x {bh}')
+    if K > 1:
+        one = _call(ctx, frames[K - 1:], (bw, bh))
+        for key in ('sub', 'back', 'mesh_back', 'mesh_rms', 'globalback', 'globalrms', 'status'):
+            assert np.array_equal(one[key][0], got[key][K - 1]), key
+    # lc_background_map on its own, through mesh values that are not the device's: the restatement's, back and rms
+    for key in ('mesh_back', 'mesh_rms'):
+        mesh = np.stack([wt[key] for wt in wants]).astype(np.float32)
+        maps = sep.background_map(mesh, h, w, bw, bh, ctx=ctx)
+        assert maps.shape == (K, h, w) and maps.dtype == np.float32
+        for k in range(K):
+            err = np.abs(maps[k] - B.spline_map(mesh[k], h, w, bw, bh, np.float64)).max()
+            print(f'{h} x {w} in {bw} x {bh}: lc_background_map of {key} {err / np.abs(mesh[k]).max():.3g} of the largest value')
+            assert err <= 2e-5 * np.abs(mesh[k]).max(), key
+    # the sep mirror
+    bkg = sep.Background(frames[0], bw=bw, bh=bh, ctx=ctx)
+    assert bkg.mesh_back.shape == (1,) + shape and np.array_equal(bkg.mesh_back[0], got['mesh_back'][0])
+    assert bkg.globalback == float(got['globalback'][0]) and bkg.globalrms == float(got['globalrms'][0])
+    assert np.array_equal(bkg.back(), got['back'][0]) and np.array_equal(frames[0] - bkg, got['sub'][0])
+    want_rms = B.spline_map(got['mesh_rms'][0], h, w, bw, bh, np.float64)
+    assert bkg.rms().shape == (h, w) and np.abs(bkg.rms() - want_rms).max() <= 2e-5 * got['mesh_rms'][0].max()
+    if K > 1:
+        stack = sep.Background(frames, bw=bw, bh=bh, ctx=ctx)
+        assert np.array_equal(stack.globalback, got['globalback']) and np.array_equal(frames - stack, got['sub'])
+    if (bw, bh) in ((13, 65), (65, 13)):        # the masked case: whole meshes bad and filled, scattered pixels
+        mask = B.unequal_mask(h, w)
+        want = B.background(frames[0], mask=mask, bw=bw, bh=bh, maps=False)
+        assert want['paths']['filled'] >= 3
+        masked = _call(ctx, frames[:1], (bw, bh), mask=mask[None])
+        _check_meshes(masked, 0, want, bounds, f'masked, {bw} x {bh}')
+        _check_map(masked, 0, frames[0], (bw, bh), f'masked, {bw} x {bh}')
+        assert not np.array_equal(masked['mesh_back'], got['mesh_back'][:1])
+        mirror = sep.Background(frames[0], mask=mask, bw=bw, bh=bh, ctx=ctx)
+        assert np.array_equal(mirror.mesh_back[0], masked['mesh_back'][0])
 
 
 def test_one_pixel_meshes_constant_and_integer_frames(ctx, bounds):

@@ -212,3 +212,34 @@ def test_library_reports_the_stamp_size_range():
     lib = _lib.lib()
     assert [n for n in range(0, 200) if lib.lc_ccdmask_supported(n)] == list(range(8, 129))
     assert supported(24) and supported(33) and not supported(7) and not supported(129)
+
+
+@pytest.mark.parametrize('n,K', CM.SETTINGS_SIZES)
+def test_every_settings_case_changes_the_restatement(n, K):
+    """The condition of CM.settings_cases: every case gives another ``mask`` than lsigma = hsigma = 9, ngood = 5 on its
+    input, so a kernel that ignored the setting would fail the device comparison of tests/test_ccdmask_gpu.py."""
+    d, base, cases = CM.settings_wanted(n, K)
+    assert [kw for kw, _ in cases] == CM.settings_cases(n) and len(cases) == 13
+    by = {}
+    for kw, want in cases:
+        changed = (want['mask'] != base['mask']).sum()
+        print(f'n={n} {kw}: mask pixels changed {changed}, filled {(want["mask"] & ~want["mask4"]).sum()}, lines '
+              f'{want["bad_cols"].sum() + want["bad_rows"].sum()}')
+        assert changed > 0, kw
+        by[tuple(sorted(kw.items()))] = want
+    ngood = lambda g: by[(('ngood', g),)]
+    # from n - 1 on no line can start a fill: the mask of ngood 0, which is the mask of the threshold
+    for g in (n - 1, n, n + 5):
+        assert np.array_equal(ngood(g)['mask'], ngood(0)['mask']), g
+    assert np.array_equal(ngood(0)['mask'], base['mask4'])
+    # n - 2 is the last value at which the fill runs (from line 0 alone), and there it reads the last row: with the low
+    # thresholds of the combined case it fills, and some of that hangs on the last row alone
+    last = by[(('hsigma', 2), ('lsigma', 2), ('ngood', n - 2))]
+    assert (last['mask'] & ~last['mask4']).any()
+    blind = last['mask4'].copy()
+    blind[:, -1, :] = False
+    assert not np.array_equal(CM.fill_short_gaps(blind, n - 2)[:, :-1], last['mask'][:, :-1])
+    assert not np.array_equal(last['mask'], CM.ccdmask(d, lsigma=2, hsigma=2, ngood=n - 1)['mask'])
+    # a swap of the two thresholds would show: the asymmetric pair is not its mirror image
+    assert not np.array_equal(by[(('hsigma', 20), ('lsigma', 3))]['mask'], CM.ccdmask(d, lsigma=20, hsigma=3)['mask'])
+    assert not np.array_equal(by[(('lsigma', 3),)]['mask'], by[(('hsigma', 3),)]['mask'])

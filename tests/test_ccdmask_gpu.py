@@ -1,8 +1,9 @@
 """lc_ccdmask_stamps and lc_mask_cutouts on the device against the float32 NumPy restatement of the SPEC
 (tests/_ccdmask.py, DESIGN.md §5 "Bad rows and columns"): mask, rowcol, bad_cols and bad_rows exactly and sigma
 numerically at every stamp-size class (even and odd, 36 KiB to 144 KiB of LDS planes, K = 1), the hand cases of the
-column fill, the ccdproc-shaped shim, and mask_cutout_batch against the two separate calls and through the chain
-mask_cutout_batch -> lc_prepare_stamps -> build_psf_batch."""
+column fill, lsigma, hsigma and ngood away from 9 / 9 / 5 (CM.settings_cases), the ccdproc-shaped shim, and
+mask_cutout_batch against the two separate calls and through the chain mask_cutout_batch -> lc_prepare_stamps ->
+build_psf_batch."""
 import numpy as np
 import pytest
 
@@ -71,6 +72,30 @@ def test_without_findbadcolumns_the_mask_is_that_of_the_threshold(ctx):
     got = ccdmask(d, ctx=ctx)
     assert got.dtype == bool and got.shape == d.shape and np.array_equal(got, want['mask4'])
     assert np.array_equal(ccdmask(d, findbadcolumns=True, ctx=ctx), want['mask'])
+
+
+@pytest.mark.parametrize('n,K', CM.SETTINGS_SIZES)
+def test_settings_other_than_the_defaults(ctx, n, K):
+    """Every case of CM.settings_cases, all five outputs exactly, then through the ccdproc-shaped call with
+    findbadcolumns both ways.  Each case changes the restatement's mask against the defaults
+    (tests/test_ccdmask_cpu.py asserts that), so a kernel that ignored a threshold, swapped the two or ran the fill
+    loop one line short or long fails here."""
+    from lightcurver_amd.ccdproc import ccdmask, ccdmask_stamps
+    d, base, cases = CM.settings_wanted(n, K)
+    wrong = []
+    for kw, want in cases:
+        got = ccdmask_stamps(d, ctx=ctx, **kw)
+        same = {key: bool(got[key].dtype == bool and np.array_equal(got[key], want[key]))
+                for key in ('mask', 'rowcol', 'bad_cols', 'bad_rows')}
+        same['sigma'] = bool(got['sigma'].dtype == np.float32 and np.array_equal(got['sigma'], want['sigma'], equal_nan=True))
+        same['ccdmask(findbadcolumns=True)'] = np.array_equal(ccdmask(d, findbadcolumns=True, ctx=ctx, **kw), want['mask'])
+        same['ccdmask()'] = np.array_equal(ccdmask(d, ctx=ctx, **kw), want['mask4'])
+        print(f'n={n} K={K} {kw}: mask {want["mask"].sum()} / device {got["mask"].sum()} (defaults {base["mask"].sum()}), '
+              f'filled {(want["mask"] & ~want["mask4"]).sum()}, lines {want["bad_cols"].sum() + want["bad_rows"].sum()} / '
+              f'device {got["bad_cols"].sum() + got["bad_rows"].sum()}')
+        if not all(same.values()):
+            wrong.append((kw, [key for key, ok in same.items() if not ok]))
+    assert not wrong, wrong
 
 
 def test_single_stamp_calls_equal_the_batched_call(ctx):

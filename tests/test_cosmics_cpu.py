@@ -261,3 +261,53 @@ def test_library_reports_the_stamp_size_range():
     lib = _lib.lib()
     assert [n for n in range(0, 200) if lib.lc_cosmics_supported(n)] == list(range(8, 129))
     assert supported(24) and supported(33) and not supported(7) and not supported(129)
+
+
+@pytest.mark.parametrize('n,K,with_invar,sepmed', LA.SETTINGS_INPUTS)
+def test_every_settings_case_changes_the_restatement(n, K, with_invar, sepmed):
+    """The condition of the settings lists (LA.SETTINGS, LA.SETTINGS_VARIANTS): on its input every case gives another
+    result than its base (the defaults, or the defaults with the one setting named in the case), in the output the
+    case names: a kernel that ignored the setting would fail the device comparison of tests/test_cosmics_gpu.py."""
+    cases = LA.settings_wanted(n, K, with_invar, sepmed)
+    assert [c[0] for c in cases] == [c[0] for c in LA.settings_cases(n, K, with_invar, sepmed)]
+    for label, d, kw, want, base in cases:
+        changed = (want['crmask'] != base['crmask']).sum()
+        print(f'n={n} invar={with_invar} sepmed={sepmed} {label}: crmask pixels changed {changed}, clean '
+              f'{(want["clean"].view(np.uint32) != base["clean"].view(np.uint32)).sum()}, flagged {want["crmask"].sum()}, '
+              f'iters {np.bincount(want["iters"]).tolist()}')
+        assert LA.settings_differ(label, want, base), label
+    by = {c[0]: c for c in cases}
+    if 'niter 1' in by:        # some stamp's mask differs between niter 1 and niter 4
+        label, d, kw, want, base = by['niter 1']
+        assert (want['crmask'] != base['crmask']).reshape(K, -1).any(axis=1).any() and want['iters'].max() == 1
+    label, d, kw, want, base = by['sigclip 0.5 objlim 0.5']
+    assert np.all(want['iters'] == 4) and want['crmask'].sum() > 20 * base['crmask'].sum()   # the load case of meanmask
+
+
+def test_settings_lists_cover_every_setting():
+    """No case disappears quietly: a label is left out of an input only where LA.SETTINGS_NOT_MET names it, which is at
+    n = 65 alone, so every label runs on all eight inputs of the two LDS sizes and at n = 65 at least once."""
+    for key in LA.SETTINGS_INPUTS:
+        other = LA.SETTINGS_VARIANTS[key]
+        assert set(other) <= set(LA.SETTINGS)
+        assert {label for label, spec in other.items() if spec is None} == LA.SETTINGS_NOT_MET.get(key, set()), key
+        ran = LA.settings_cases(*key)
+        assert [c[0] for c in ran] == [label for label in LA.SETTINGS if label not in LA.SETTINGS_NOT_MET.get(key, set())]
+        for label, variant, seed in ran:
+            assert variant in ('plain', 'blocks') or key[2], (key, label)     # the holes are holes of invar
+            assert seed is None or seed != 10 * key[0] + key[1]
+    assert all(key[0] == 65 for key in LA.SETTINGS_NOT_MET) and set(LA.SETTINGS_NOT_MET) <= set(LA.SETTINGS_INPUTS)
+    at65 = set().union(*({c[0] for c in LA.settings_cases(*key)} for key in LA.SETTINGS_INPUTS if key[0] == 65))
+    assert at65 == set(LA.SETTINGS)
+
+
+def test_configuration_path_refuses_without_a_device():
+    from lightcurver_amd.processes.cutout_making import mask_cosmics_batch, mask_cutout_batch
+    d = np.ones((2, 16, 16), np.float32)
+    for params, err in ((dict(cleantype='median'), NotImplementedError), (dict(sigclipp=3.0), TypeError)):
+        with pytest.raises(err):
+            mask_cutout_batch(d, d, False, True, params)
+        with pytest.raises(err):
+            mask_cutout_batch(d, d, True, True, params)
+        with pytest.raises(err):
+            mask_cosmics_batch(d, d, params)

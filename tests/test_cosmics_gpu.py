@@ -1,7 +1,8 @@
 """lc_detect_cosmics on the device against the float32 NumPy restatement of the SPEC (tests/_lacosmic.py, DESIGN.md §5
 "Cosmic-ray detection"): crmask, clean and iters bit for bit, both median modes, every stamp-size class (LDS planes up
 to 64, global planes above, odd sizes), with and without invar, with inmask, NaN borders and saturated cores; then the
-single-stamp form against the batched one, and the chain mask_cosmics_batch -> lc_prepare_stamps -> build_psf_batch."""
+single-stamp form against the batched one, the chain mask_cosmics_batch -> lc_prepare_stamps -> build_psf_batch, and every
+setting away from its default (LA.SETTINGS), also as cosmics_masking_params through mask_cutout_batch."""
 import numpy as np
 import pytest
 
@@ -12,27 +13,7 @@ pytestmark = pytest.mark.gpu
 SIZES_K = [(8, 800), (16, 300), (24, 1), (25, 120), (32, 200), (33, 80), (64, 40), (65, 24), (128, 6)]
 
 
-def _stamps(K, n, seed, electrons):
-    """K star stamps of make_psf_dataset (electrons: unscaled, for the noise model without invar) with 0 - 3 injected
-    cosmics each, 1 % inmask, a partial-cutout NaN border on every fifth stamp; satlevel cuts into the brightest cores."""
-    from lightcurver_amd.synthetic import make_psf_dataset
-    S = 8
-    ds = make_psf_dataset(F=(K + S - 1) // S, S=S, n=n, seed=seed)
-    scale = np.float32(ds['scale']) if electrons else np.float32(1.0)
-    d = (ds['data'].reshape(-1, n, n)[:K] * scale).astype(np.float32)
-    nm = (ds['noisemap'].reshape(-1, n, n)[:K] * scale).astype(np.float32)
-    rng = np.random.default_rng(seed + 1)
-    d, _ = LA.inject_cosmics(d, nm, rng)
-    inmask = rng.uniform(size=d.shape) < 0.01
-    w = max(1, n // 5)
-    for k in range(0, K, 5):
-        side = k // 5 % 4
-        sl = [(slice(None), slice(0, w)), (slice(0, w), slice(None)), (slice(None), slice(n - w, n)),
-              (slice(n - w, n), slice(None))][side]
-        d[k][sl] = np.nan
-        nm[k][sl] = np.nan
-    satlevel = float(np.nanpercentile(d, 99.8))
-    return d, nm, inmask, satlevel
+_stamps = LA.star_stamps        # the inputs, shared with the settings lists of tests/_lacosmic.py
 
 
 def _same(a, b):
@@ -139,6 +120,62 @@ def test_mask_cosmics_batch_feeds_prepare_stamps_and_build_psf(ctx):
     for g, w in zip(got, want):
         assert np.all(np.isfinite(g['narrow_psf']))
         assert np.array_equal(g['narrow_psf'], w['narrow_psf']) and np.array_equal(g['full_psf'], w['full_psf'])
+
+
+@pytest.mark.parametrize('n,K,with_invar,sepmed', LA.SETTINGS_INPUTS)
+def test_settings_other_than_the_defaults(ctx, n, K, with_invar, sepmed):
+    """Every case of LA.SETTINGS that applies to this input (LA.settings_cases), bit for bit.  Each changes the
+    restatement's result against its base (tests/test_cosmics_cpu.py asserts that), so a kernel that ignored or mixed
+    up a setting fails here.  With invar, readnoise is told apart through the invalid pixels alone, at sigclip 1; values
+    far above the noise of every pixel (30 against 6.5 on the scaled stamps) are not told apart by any input we found,
+    so 30 runs on the stamps in electrons there."""
+    from lightcurver_amd.astroscrappy import lacosmic
+    wrong = []
+    for label, d, kw, want, base in LA.settings_wanted(n, K, with_invar, sepmed):
+        got = lacosmic(d, ctx=ctx, **kw)
+        same = (np.array_equal(got['crmask'], want['crmask']), _same(got['clean'], want['clean'].astype(np.float32)),
+                np.array_equal(got['iters'], want['iters']))
+        print(f'n={n} K={K} invar={with_invar} sepmed={sepmed} {label}: flagged {want["crmask"].sum()} / device '
+              f'{got["crmask"].sum()} (base {base["crmask"].sum()}), iters {np.bincount(want["iters"]).tolist()} / device '
+              f'{np.bincount(got["iters"]).tolist()}, crmask, clean, iters equal: {same}')
+        if not all(same):
+            wrong.append((label, same))
+    assert not wrong, wrong
+
+
+def test_configuration_path_takes_the_users_settings(ctx):
+    """cosmics_masking_params as a user writes them in the configuration (a raised objlim, fewer iterations, the keys
+    of fsmode='convolve' that have no effect) through mask_cutout_batch and mask_cosmics_batch: the restatement with
+    those values, ORed with the row / column half where that is on."""
+    from tests import _ccdmask as CM
+    from lightcurver_amd.processes.cutout_making import mask_cosmics_batch, mask_cutout_batch
+    user = dict(objlim=8, sigclip=3, niter=2)
+    params = dict(user, verbose=False, psffwhm=2.5)
+    sets = {}
+    for n, K in ((24, 16), (65, 4)):
+        d, nm = CM.star_stamps(n, F=(K + 7) // 8, seed=n + 40)
+        d, nm = d[:K], nm[:K]
+        d, _, _ = CM.inject_lines(d, nm, np.random.default_rng(n + 41))
+        d, _ = LA.inject_cosmics(d, nm, np.random.default_rng(n + 42))
+        cosmics = LA.lacosmic(d, invar=nm ** 2, **user)['crmask']
+        lines = CM.ccdmask(d)['rowcol']
+        assert not np.array_equal(cosmics, LA.lacosmic(d, invar=nm ** 2)['crmask'])       # the settings matter here
+        assert cosmics.any() and lines.any() and (cosmics & ~lines).any()
+        assert np.array_equal(mask_cutout_batch(d, nm, False, True, params, ctx=ctx), cosmics)
+        assert np.array_equal(mask_cutout_batch(d, nm, True, True, params, ctx=ctx), cosmics | lines)
+        assert np.array_equal(mask_cutout_batch(d, nm, True, False, params, ctx=ctx), lines)
+        assert np.array_equal(mask_cosmics_batch(d, nm, params, ctx=ctx), cosmics)
+        sets[n] = d, nm, cosmics | lines
+    mixed = mask_cutout_batch([sets[24][0][0], sets[65][0][1], sets[24][0][2]],
+                              [sets[24][1][0], sets[65][1][1], sets[24][1][2]], True, True, params, ctx=ctx)
+    assert all(np.array_equal(m, w) for m, w in zip(mixed, (sets[24][2][0], sets[65][2][1], sets[24][2][2])))
+    d, nm, _ = sets[24]
+    assert params == dict(user, verbose=False, psffwhm=2.5)                               # the caller's dict is left alone
+    for bad, err in ((dict(user, cleantype='median'), NotImplementedError), (dict(user, sigclipp=3.0), TypeError)):
+        with pytest.raises(err):
+            mask_cutout_batch(d, nm, True, True, bad, ctx=ctx)
+        with pytest.raises(err):
+            mask_cosmics_batch(d, nm, bad, ctx=ctx)
 
 
 def test_library_refuses_what_is_not_built(ctx):

@@ -4,6 +4,7 @@ generator's coverage of every path, and the size query of the library."""
 from fractions import Fraction
 
 import numpy as np
+import pytest
 
 from tests import _segment as SG
 
@@ -108,3 +109,27 @@ def test_segment_supported_needs_no_device():
     lib = _lib.lib()
     assert [n for n in range(0, 140) if lib.lc_segment_supported(n)] == list(range(8, 65))
     assert _lib.SEGMENT_MAX_OBJECTS == SG.OBJ_CAP == 32
+
+
+@pytest.mark.parametrize('n,K', SG.SETTINGS_SIZES)
+def test_every_settings_case_changes_the_restatement(n, K):
+    """The condition of SG.SETTINGS: every case gives another segmap than its base and than the defaults on its input
+    (and stays inside the tables: status 0), so a kernel that ignored the setting would fail the device comparison of
+    tests/test_segment_gpu.py."""
+    cases = SG.settings_wanted(n, K)
+    assert len(cases) == sum(n in sizes for _, _, _, sizes in SG.SETTINGS) >= len(SG.SETTINGS) - 1
+    for kw, d, s, want, base, plain in cases:
+        diff = (want['segmap'] != base['segmap']).any(axis=(1, 2))
+        print(f'n={n} {kw}: stamps whose segmap differs from the base {diff.sum()} of {K}, from the defaults '
+              f'{(want["segmap"] != plain["segmap"]).any(axis=(1, 2)).sum()}; objects {np.bincount(want["nobj"]).tolist()}, '
+              f'status {np.bincount(want["status"]).tolist()}')
+        assert diff.any() and not np.array_equal(want['segmap'], plain['segmap']), kw
+        assert np.all(want['status'] == 0), kw
+    by = {tuple(sorted(kw.items())): (want, base) for kw, d, s, want, base, plain in cases}
+    want, base = by[(('deblend_cont', 0.05),)]
+    assert (want['nobj'][0::2] < base['nobj'][0::2]).any()          # 0.05 merges what 0.001 splits: the 1 % secondaries
+    want, base = by[(('clean', False), ('deblend_cont', 1e-06))]
+    assert (want['nobj'][1::2] > base['nobj'][1::2]).any()          # 1e-6 splits what 0.001 merges: the faint ones
+    want, base = by[(('deblend_cont', 1e-05), ('minarea', 3), ('thresh', 1.5))]
+    assert want['nobj'].max() >= 7
+    assert all(n in sizes for _, _, _, sizes in SG.SETTINGS if sizes != (24,))

@@ -1,6 +1,7 @@
 """lc_segment_stamps on the device against the NumPy restatement of the SPEC (tests/_segment.py, DESIGN.md §5 "Source
-masking"): mask, segmap, nobj, status and the float32 barycentres bit for bit at every stamp-size class; the full
-table; single against batched calls; mixed sizes; the host route for large stamps; the chain into the PSF fit."""
+masking"): mask, segmap, nobj, status and the float32 barycentres bit for bit at every stamp-size class; every
+setting away from its default (SG.SETTINGS); the full table; single against batched calls; mixed sizes; the host route
+for large stamps; the chain into the PSF fit."""
 import ctypes as C
 
 import numpy as np
@@ -43,6 +44,26 @@ def test_bit_equal_to_the_restatement(ctx, n, K):
     if n in (24, 32):
         assert took['merged'] > 0
     _check(got, want)
+
+
+@pytest.mark.parametrize('n,K', SG.SETTINGS_SIZES)
+def test_settings_other_than_the_defaults(ctx, n, K):
+    """Every case of SG.SETTINGS at this size, bit for bit.  Each changes the restatement's segmap against its base and
+    against the defaults (tests/test_segment_cpu.py asserts that), so a kernel that ignored a setting fails here."""
+    from lightcurver_amd.processes.source_masking import segment_batch
+    wrong = []
+    for kw, d, s, want, base, plain in SG.settings_wanted(n, K):
+        args = {('clean_detections' if key == 'clean' else key): v for key, v in kw.items()}
+        got = segment_batch(d, s, ctx=ctx, **args)
+        same = dict(status=np.array_equal(got['status'], want['status']), nobj=np.array_equal(got['nobj'], want['nobj']),
+                    segmap=got['segmap'].dtype == np.int32 and np.array_equal(got['segmap'], want['segmap']),
+                    mask=got['mask'].dtype == bool and np.array_equal(got['mask'], want['mask']),
+                    xy=_same(got['xy'], want['xy']))
+        print(f'n={n} K={K} {kw}: objects {np.bincount(want["nobj"]).tolist()} / device {np.bincount(got["nobj"]).tolist()} '
+              f'(base {np.bincount(base["nobj"]).tolist()}), device status {np.bincount(got["status"]).tolist()}')
+        if not all(same.values()):
+            wrong.append((kw, [key for key, ok in same.items() if not ok]))
+    assert not wrong, wrong
 
 
 def test_full_table_is_reported_and_leaves_the_batch_untouched(ctx):

@@ -270,6 +270,49 @@ int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const 
                      int32_t *bg_status /*nullable*/, lc_extract_object *objects, int32_t *nobj,
                      int32_t *segmap /*nullable*/, int32_t *ex_status, float *kernel_ms /*nullable*/);
 
+/* ---- a frame set that stays on the device, and the stamps cut from it -----------------------------------------
+ * Reference: lightcurver/processes/cutout_making.py:23-51 (extract_stamp: Cutout2D(mode='partial', fill_value=nan) and the
+ * noise map, once per stamp, called at :188 for the ROI and :238 for each star) on the sky-subtracted frame that
+ * frame_importation.py:119 wrote.  Here the frames are uploaded once, imported where they lie, and every stamp of one
+ * size is cut in one call (DESIGN.md section 5 "Stamp cutting").
+ *   lc_frames_create   K frames of h x w, row-major float32, copied to the device; the object belongs to ctx and is
+ *     destroyed before it.  lc_frames_get copies planes [first, first + count) back as they are now.
+ *   lc_frames_import   what lc_import_frames runs, on the resident planes, with the same arguments, outputs and error
+ *     codes after `exptime`; sub may be NULL.  Afterwards the resident planes are sub, the raw planes are freed and
+ *     exptime and globalrms stay recorded on the device (lc_frames_info: imported = 1).  If a frame's object table was
+ *     too small (ex_status 1) the call still returns LC_OK with every output filled, but the set stays as it was
+ *     (imported = 0), so that the caller can import again with a larger max_objects.  LC_ERR_INVALID for a set that is
+ *     imported already.  During the call the device holds sub and four more planes of scratch beside the raw frames.
+ *   lc_frames_cut_stamps   S stamps of n x n in one call: stamp s has its corner at (y0[s], x0[s]) of frame frame[s]
+ *     (frames in any order, repeated at will), pixel (i, j) = frame pixel (y0 + i, x0 + j), NaN outside the frame.
+ *     noisemap_out = max(sqrt((t rms)^2 + |t data|), 1e-7) / t in the float32 steps of lc_prepare_stamps, NaN where data
+ *     is; exptime (t) and rms [K] per frame of the set, each may be NULL after an import (the recorded values are used).
+ *     mask_out: what lc_mask_cutouts returns for data_out and noisemap_out with the same switches and settings, formed
+ *     on the stamps where they lie on the device; both switches off gives a zero mask.  n_inside [S]: pixels of the stamp
+ *     that lie in the frame.  kernel_ms = device time of all kernels (HIP events).
+ *     Checked on the host before anything is launched, LC_ERR_INVALID: S or n < 1, a missing pointer (data_out; mask_out
+ *     with a switch on; the settings of a switch that is on), a frame index outside [0, K), a stamp without one pixel
+ *     in the frame, an exptime that is not finite or not > 0, no exptime or rms (given or recorded) when noisemap_out
+ *     or a switch is set.  LC_ERR_UNSUPPORTED: S n n >= 2^31; with a switch on, n outside 8 .. 128 and what the two mask
+ *     calls refuse.  lc_cutout_supported(n, with_masks) answers for one stamp (1 / 0) without a device. */
+typedef struct lc_frames lc_frames;
+int lc_frames_create(lc_ctx *ctx, int K, int h, int w, const float *data /*[K][h][w]*/, lc_frames **out);
+void lc_frames_destroy(lc_frames *f);
+int lc_frames_info(lc_frames *f, int *K, int *h, int *w, int *imported); /* each may be NULL */
+int lc_frames_get(lc_frames *f, int first, int count, float *out /*[count][h][w]*/);
+int lc_frames_import(lc_frames *f, const float *exptime /*[K]*/, const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg,
+                     int mask_sources_first, const lc_extract_cfg *mcfg /*read when mask_sources_first*/, int max_objects,
+                     float *sub /*nullable*/, float *mesh_back /*nullable*/, float *mesh_rms /*nullable*/, float *globalback,
+                     float *globalrms, int32_t *bg_status /*nullable*/, lc_extract_object *objects, int32_t *nobj,
+                     int32_t *segmap /*nullable*/, int32_t *ex_status, float *kernel_ms /*nullable*/);
+int lc_cutout_supported(int n, int with_masks);
+int lc_frames_cut_stamps(lc_frames *f, int S, int n, const int32_t *frame /*[S]*/, const int32_t *y0 /*[S]*/,
+                         const int32_t *x0 /*[S]*/, const float *exptime /*[K], nullable after an import*/,
+                         const float *rms /*[K], nullable after an import*/, int do_bad_columns, int do_cosmics,
+                         const lc_cosmics_cfg *cosmics_cfg /*nullable*/, const lc_ccdmask_cfg *ccdmask_cfg /*nullable*/,
+                         float *data_out /*[S][n][n]*/, float *noisemap_out /*nullable*/, uint8_t *mask_out /*nullable*/,
+                         int32_t *n_inside /*[S] nullable*/, float *kernel_ms /*nullable*/);
+
 /* ---- optimiser settings shared by both fits ----------------------------------------------- */
 /* optax.adabelief as driven by STARRED's Optimizer(method='adabelief'):
  * lightcurver/processes/star_photometry.py:113-122, roi_modelling.py:326-334. */

@@ -116,6 +116,15 @@ SIGNATURES = {
     'lc_import_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(BackgroundCfg), C.POINTER(ExtractCfg),
                                    C.c_int, C.POINTER(ExtractCfg), C.c_int, fp, fp, fp, fp, fp, ip, vp, ip, ip, ip,
                                    C.POINTER(C.c_float)]),
+    'lc_frames_create': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, C.POINTER(vp)]),
+    'lc_frames_destroy': (None, [vp]),
+    'lc_frames_info': (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'lc_frames_get': (C.c_int, [vp, C.c_int, C.c_int, fp]),
+    'lc_frames_import': (C.c_int, [vp, fp, C.POINTER(BackgroundCfg), C.POINTER(ExtractCfg), C.c_int, C.POINTER(ExtractCfg),
+                                   C.c_int, fp, fp, fp, fp, fp, ip, vp, ip, ip, ip, C.POINTER(C.c_float)]),
+    'lc_cutout_supported': (C.c_int, [C.c_int, C.c_int]),
+    'lc_frames_cut_stamps': (C.c_int, [vp, C.c_int, C.c_int, ip, ip, ip, fp, fp, C.c_int, C.c_int, C.POINTER(CosmicsCfg),
+                                       C.POINTER(CcdmaskCfg), fp, fp, C.POINTER(C.c_uint8), ip, C.POINTER(C.c_float)]),
     'lc_ctx_stream': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     'lc_ctx_synchronize': (C.c_int, [vp]),
     'lc_timer_start': (C.c_int, [vp]),

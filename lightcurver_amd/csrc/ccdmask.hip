@@ -17,6 +17,7 @@
 #include "cosmics_device.h"
 #include "device_call.h"
 #include "lc_common.h"
+#include "mask_steps.h"
 #include "../../include/lcmi.h"
 
 namespace lc {
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(256) void or_kernel(uint8_t *a, const uint8_t *b, s
   if (i < count) a[i] |= b[i];
 }
 
-static int ccdmask_check(lc_ctx *ctx, const char *who, int n, const lc_ccdmask_cfg *cfg) {
+int ccdmask_check(lc_ctx *ctx, const char *who, int n, const lc_ccdmask_cfg *cfg) {
   const std::string w(who);
   if (n < kCmMinN || n > kCmMaxN) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, w + ": stamp size outside 8 .. 128");
   if (cfg->byblocks != 0) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, w + ": byblocks is not built");
@@ -262,8 +263,8 @@ static void percentile_ranks(float p, int count, int *lo, int *hi, float *t) {
 }
 
 // one launch on ctx->stream over K stamps; every pointer is a device pointer, any output may be null
-static hipError_t ccdmask_launch(lc_ctx *ctx, int K, int n, const float *data, const lc_ccdmask_cfg *cfg, uint8_t *mask,
-                                 uint8_t *rowcol, uint8_t *bad_cols, uint8_t *bad_rows, float *sigma) {
+hipError_t ccdmask_launch(lc_ctx *ctx, int K, int n, const float *data, const lc_ccdmask_cfg *cfg, uint8_t *mask,
+                          uint8_t *rowcol, uint8_t *bad_cols, uint8_t *bad_rows, float *sigma) {
   CmArgs A;
   std::memset(&A, 0, sizeof(A));
   A.n = n;
@@ -285,6 +286,45 @@ static hipError_t ccdmask_launch(lc_ctx *ctx, int K, int n, const float *data, c
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(ccdmask_kernel, dim3(K), dim3(kCmThreads), lds_bytes, ctx->stream, A);
   return hipGetLastError();
+}
+
+hipError_t square_launch(lc_ctx *ctx, const float *x, float *y, size_t count) {
+  hipLaunchKernelGGL(square_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, x, y, count);
+  return hipGetLastError();
+}
+
+hipError_t or_launch(lc_ctx *ctx, uint8_t *a, const uint8_t *b, size_t count) {
+  hipLaunchKernelGGL(or_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, a, b, count);
+  return hipGetLastError();
+}
+
+hipError_t mask_cutouts_scratch(DeviceCall &call, const lc_ctx *ctx, int K, int n, int do_bad_columns, int do_cosmics,
+                                MaskCutoutsScratch *S) {
+  if (!do_cosmics) return hipSuccess;
+  const size_t tot = (size_t)K * n * n;
+  hipError_t e = call.alloc(tot, &S->invar);
+  if (e != hipSuccess) return e;
+  if (const size_t sb = cosmics_scratch_bytes(ctx, K, n))
+    if ((e = call.alloc(sb / 4, &S->cosmics)) != hipSuccess) return e;
+  return do_bad_columns ? call.alloc(tot, &S->lines) : hipSuccess;
+}
+
+hipError_t mask_cutouts_launch(lc_ctx *ctx, int K, int n, const float *data, const float *noisemap, int do_bad_columns,
+                               int do_cosmics, const lc_cosmics_cfg *cosmics_cfg, const lc_ccdmask_cfg *ccdmask_cfg,
+                               const MaskCutoutsScratch &S, uint8_t *mask) {
+  const size_t tot = (size_t)K * n * n;
+  hipError_t e = hipSuccess;
+  if (do_cosmics) {
+    if ((e = square_launch(ctx, noisemap, S.invar, tot)) != hipSuccess) return e;
+    e = cosmics_launch(ctx, K, n, data, S.invar, nullptr, cosmics_cfg, mask, nullptr, nullptr, S.cosmics);
+    if (e != hipSuccess) return e;
+  }
+  if (do_bad_columns) {
+    uint8_t *rowcol = do_cosmics ? S.lines : mask;
+    if ((e = ccdmask_launch(ctx, K, n, data, ccdmask_cfg, nullptr, rowcol, nullptr, nullptr, nullptr)) != hipSuccess) return e;
+    if (do_cosmics) e = or_launch(ctx, mask, S.lines, tot);
+  }
+  return e;
 }
 
 }  // namespace lc
@@ -339,31 +379,15 @@ int lc_mask_cutouts(lc_ctx *ctx, int K, int n, const float *data, const float *n
   LC_ENTER(ctx);
   DeviceCall call(ctx);
   const float *d_data = nullptr;
-  float *d_invar = nullptr, *d_scratch = nullptr;
-  uint8_t *d_mask = nullptr, *d_lines = nullptr;
+  uint8_t *d_mask = nullptr;
+  MaskCutoutsScratch S;
   LC_HIP(ctx, call.upload(data, tot, &d_data));
   LC_HIP(ctx, call.result(mask, tot, &d_mask));
-  if (do_cosmics) {
-    LC_HIP(ctx, call.alloc(tot, &d_invar));  // the noise map, squared in place: not upload()'s read-only input
-    LC_HIP(ctx, hipMemcpyAsync(d_invar, noisemap, tot * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (const size_t sb = cosmics_scratch_bytes(ctx, K, n)) LC_HIP(ctx, call.alloc(sb / 4, &d_scratch));
-    if (do_bad_columns) LC_HIP(ctx, call.alloc(tot, &d_lines));
-  }
-  const unsigned blocks = (unsigned)((tot + 255) / 256);
+  LC_HIP(ctx, mask_cutouts_scratch(call, ctx, K, n, do_bad_columns, do_cosmics, &S));
+  if (do_cosmics)  // the noise map goes where it is squared in place: not upload()'s read-only input
+    LC_HIP(ctx, hipMemcpyAsync(S.invar, noisemap, tot * 4, hipMemcpyHostToDevice, ctx->stream));
   LC_HIP(ctx, call.start());
-  if (do_cosmics) {
-    hipLaunchKernelGGL(square_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_invar, d_invar, tot);
-    LC_HIP(ctx, hipGetLastError());
-    LC_HIP(ctx, cosmics_launch(ctx, K, n, d_data, d_invar, nullptr, cosmics_cfg, d_mask, nullptr, nullptr, d_scratch));
-  }
-  if (do_bad_columns) {
-    uint8_t *rowcol = do_cosmics ? d_lines : d_mask;
-    LC_HIP(ctx, ccdmask_launch(ctx, K, n, d_data, ccdmask_cfg, nullptr, rowcol, nullptr, nullptr, nullptr));
-    if (do_cosmics) {
-      hipLaunchKernelGGL(or_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_mask, d_lines, tot);
-      LC_HIP(ctx, hipGetLastError());
-    }
-  }
+  LC_HIP(ctx, mask_cutouts_launch(ctx, K, n, d_data, S.invar, do_bad_columns, do_cosmics, cosmics_cfg, ccdmask_cfg, S, d_mask));
   LC_HIP(ctx, call.stop());
   LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;

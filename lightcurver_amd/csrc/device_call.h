@@ -29,6 +29,13 @@ struct DevPool {
     hipError_t e = alloc(count, d);
     return e == hipSuccess ? hipMemsetAsync(*d, 0, count * sizeof(T), stream) : e;
   }
+  // frees one buffer ahead of the pool (a null pointer, or one the pool does not hold, is left alone)
+  void release(void *p) {
+    const auto it = std::find(held.begin(), held.end(), p);
+    if (!p || it == held.end()) return;
+    held.erase(it);
+    (void)hipFree(p);
+  }
 };
 
 // One call of an entry point on ctx->stream: inputs up, ev0, kernels, ev1, outputs back, one synchronise.
@@ -36,6 +43,7 @@ struct DevPool {
 //   LC_HIP(ctx, call.upload(host_in, count, &d_in));     // a null host pointer gives a null device pointer
 //   LC_HIP(ctx, call.result(host_out, count, &d_out));   // likewise: an output the caller did not ask for
 //   LC_HIP(ctx, call.alloc(count, &d_scratch));          // neither input nor output
+//   call.download(host_out, count, d_resident);          // an output that lies in a buffer the call does not own
 //   LC_HIP(ctx, call.start());  ... launches ...  LC_HIP(ctx, call.stop());
 //   LC_HIP(ctx, call.finish(kernel_ms));
 class DeviceCall {
@@ -62,6 +70,10 @@ class DeviceCall {
     hipError_t e = pool_.alloc(count, d);
     if (e == hipSuccess) back_.push_back({host, *d, count * sizeof(T)});
     return e;
+  }
+  template <class T>
+  void download(T *host, size_t count, const T *d) {
+    if (host) back_.push_back({host, d, count * sizeof(T)});
   }
   hipError_t start() { return hipEventRecord(ctx_->ev0, ctx_->stream); }
   hipError_t stop() { return hipEventRecord(ctx_->ev1, ctx_->stream); }

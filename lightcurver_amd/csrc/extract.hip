@@ -746,6 +746,68 @@ static const char *ex_cfg_error(const lc_extract_cfg *c) {
   return nullptr;
 }
 
+int import_check(lc_ctx *ctx, const char *who, bool pointers_ok, int K, int h, int w, const float *exptime,
+                 const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg, int mask_sources_first,
+                 const lc_extract_cfg *mcfg, int max_objects) {
+  const std::string me(who);
+  if (!pointers_ok || K < 1 || h < 1 || w < 1 || !exptime || !bcfg || max_objects < 1 || bcfg->bw < 1 || bcfg->bh < 1 ||
+      !std::isfinite(bcfg->fthresh))
+    LC_FAIL(ctx, LC_ERR_INVALID, me + ": invalid argument");
+  for (int k = 0; k < K; ++k)
+    if (!std::isfinite(exptime[k]) || !(exptime[k] > 0.0f))
+      LC_FAIL(ctx, LC_ERR_INVALID, me + ": an exposure time that is not finite or not > 0");
+  if (const char *why = ex_cfg_error(ecfg)) LC_FAIL(ctx, LC_ERR_INVALID, me + ": catalogue: " + why);
+  if (mask_sources_first)
+    if (const char *why = ex_cfg_error(mcfg)) LC_FAIL(ctx, LC_ERR_INVALID, me + ": source mask: " + why);
+  if (bcfg->fthresh != 0.0f) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, me + ": fthresh other than 0 is not built");
+  if (!lc_background_supported(h, w, bcfg->bw, bcfg->bh, bcfg->fw, bcfg->fh) ||
+      !background_batch_fits(K, h, w, bcfg->bw, bcfg->bh))
+    LC_FAIL(ctx, LC_ERR_UNSUPPORTED,
+            me + ": only the 1 x 1 and 3 x 3 filters, at most 256 meshes along an axis and 2048 in all");
+  if (!lc_extract_supported(h, w) || !extract_batch_fits(K, h, w) ||
+      (int64_t)K * max_objects >= ((int64_t)1 << 31) / kExAux)
+    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, me + ": frames of 2^31 pixels or more, or more of them than one grid takes");
+  return LC_OK;
+}
+
+hipError_t import_launch(lc_ctx *ctx, int K, int h, int w, const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg,
+                         int mask_sources_first, const lc_extract_cfg *mcfg, int max_objects, ImportBuffers &I) {
+  const size_t hw = (size_t)h * w;
+  BackgroundBuffers &G = I.G;
+  ExtractBuffers &B = I.B;
+  hipError_t e = background_launch(ctx, K, h, w, bcfg, G);
+  if (e != hipSuccess) return e;
+  if (mask_sources_first) {
+    hipLaunchKernelGGL(ex_square_kernel, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, ctx->stream, K, G.globalrms, I.v0);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    ExtractBuffers Mk = B;  // the same scratch; no table, no segmap
+    Mk.data = G.sub;
+    Mk.var = nullptr;
+    Mk.var_scalar = I.v0;
+    Mk.objects = nullptr;
+    Mk.segmap = nullptr;
+    Mk.mask = I.mask;
+    Mk.nobj = I.mnobj;
+    Mk.status = I.mstatus;
+    if ((e = extract_launch(ctx, K, h, w, mcfg, max_objects, Mk)) != hipSuccess) return e;
+    G.mask = I.mask;
+    if ((e = background_launch(ctx, K, h, w, bcfg, G)) != hipSuccess) return e;
+  }
+  ExVarArgs V;
+  V.K = K;
+  V.hw = hw;
+  V.sub = G.sub;
+  V.globalrms = G.globalrms;
+  V.exptime = I.exptime;
+  V.var = I.var;
+  hipLaunchKernelGGL(ex_variance_kernel, dim3((unsigned)std::min<size_t>((hw + kExThreads - 1) / kExThreads, 4096), (unsigned)std::min(K, 65535)),
+                     dim3(kExThreads), 0, ctx->stream, V);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  B.data = G.sub;
+  B.var = I.var;
+  return extract_launch(ctx, K, h, w, ecfg, max_objects, B);
+}
+
 }  // namespace lc
 
 using namespace lc;
@@ -793,35 +855,19 @@ int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const 
                      float *globalback, float *globalrms, int32_t *bg_status, lc_extract_object *objects, int32_t *nobj,
                      int32_t *segmap, int32_t *ex_status, float *kernel_ms) {
   if (!ctx) return LC_ERR_INVALID;
-  if (K < 1 || h < 1 || w < 1 || !data || !exptime || !bcfg || !sub || !globalback || !globalrms || !objects || !nobj ||
-      !ex_status || max_objects < 1 || bcfg->bw < 1 || bcfg->bh < 1 || !std::isfinite(bcfg->fthresh))
-    LC_FAIL(ctx, LC_ERR_INVALID, "lc_import_frames: invalid argument");
-  for (int k = 0; k < K; ++k)
-    if (!std::isfinite(exptime[k]) || !(exptime[k] > 0.0f))
-      LC_FAIL(ctx, LC_ERR_INVALID, "lc_import_frames: an exposure time that is not finite or not > 0");
-  if (const char *why = ex_cfg_error(ecfg)) LC_FAIL(ctx, LC_ERR_INVALID, std::string("lc_import_frames: catalogue: ") + why);
-  if (mask_sources_first)
-    if (const char *why = ex_cfg_error(mcfg)) LC_FAIL(ctx, LC_ERR_INVALID, std::string("lc_import_frames: source mask: ") + why);
-  if (bcfg->fthresh != 0.0f) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_import_frames: fthresh other than 0 is not built");
-  if (!lc_background_supported(h, w, bcfg->bw, bcfg->bh, bcfg->fw, bcfg->fh) ||
-      !background_batch_fits(K, h, w, bcfg->bw, bcfg->bh))
-    LC_FAIL(ctx, LC_ERR_UNSUPPORTED,
-            "lc_import_frames: only the 1 x 1 and 3 x 3 filters, at most 256 meshes along an axis and 2048 in all");
-  if (!lc_extract_supported(h, w) || !extract_batch_fits(K, h, w) ||
-      (int64_t)K * max_objects >= ((int64_t)1 << 31) / kExAux)
-    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_import_frames: frames of 2^31 pixels or more, or more of them than one grid takes");
+  const bool pointers_ok = data && sub && globalback && globalrms && objects && nobj && ex_status;
+  if (int rc = import_check(ctx, "lc_import_frames", pointers_ok, K, h, w, exptime, bcfg, ecfg, mask_sources_first, mcfg,
+                            max_objects))
+    return rc;
   LC_ENTER(ctx);
   const size_t hw = (size_t)h * w, tot = (size_t)K * hw, meshes = (size_t)K * background_meshes(h, w, bcfg->bw, bcfg->bh);
   const std::vector<double> pivots = background_pivots();
   DeviceCall call(ctx);
-  BackgroundBuffers G;
-  ExtractBuffers B;
-  const float *d_exptime = nullptr;
-  float *d_var = nullptr, *d_v0 = nullptr;
-  uint8_t *d_mask = nullptr;
-  int32_t *d_mstatus = nullptr, *d_mnobj = nullptr;
+  ImportBuffers I;
+  BackgroundBuffers &G = I.G;
+  ExtractBuffers &B = I.B;
   LC_HIP(ctx, call.upload(data, tot, &G.data));
-  LC_HIP(ctx, call.upload(exptime, (size_t)K, &d_exptime));
+  LC_HIP(ctx, call.upload(exptime, (size_t)K, &I.exptime));
   LC_HIP(ctx, call.upload(pivots.data(), pivots.size(), &G.cfac));
   LC_HIP(ctx, call.result(sub, tot, &G.sub));
   LC_HIP(ctx, mesh_back ? call.result(mesh_back, meshes, &G.mesh_back) : call.alloc(meshes, &G.mesh_back));
@@ -837,44 +883,15 @@ int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const 
   LC_HIP(ctx, call.result(segmap, tot, &B.segmap));
   LC_HIP(ctx, call.result(ex_status, (size_t)K, &B.status));
   LC_HIP(ctx, extract_scratch(call, K, h, w, max_objects, true, &B));
-  LC_HIP(ctx, call.alloc(tot, &d_var));
+  LC_HIP(ctx, call.alloc(tot, &I.var));
   if (mask_sources_first) {
-    LC_HIP(ctx, call.alloc(tot, &d_mask));
-    LC_HIP(ctx, call.alloc((size_t)K, &d_v0));
-    LC_HIP(ctx, call.alloc((size_t)K, &d_mstatus));
-    LC_HIP(ctx, call.alloc((size_t)K, &d_mnobj));
+    LC_HIP(ctx, call.alloc(tot, &I.mask));
+    LC_HIP(ctx, call.alloc((size_t)K, &I.v0));
+    LC_HIP(ctx, call.alloc((size_t)K, &I.mstatus));
+    LC_HIP(ctx, call.alloc((size_t)K, &I.mnobj));
   }
   LC_HIP(ctx, call.start());
-  LC_HIP(ctx, background_launch(ctx, K, h, w, bcfg, G));
-  if (mask_sources_first) {
-    hipLaunchKernelGGL(ex_square_kernel, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, ctx->stream, K, G.globalrms, d_v0);
-    LC_HIP(ctx, hipGetLastError());
-    ExtractBuffers Mk = B;  // the same scratch; no table, no segmap
-    Mk.data = G.sub;
-    Mk.var = nullptr;
-    Mk.var_scalar = d_v0;
-    Mk.objects = nullptr;
-    Mk.segmap = nullptr;
-    Mk.mask = d_mask;
-    Mk.nobj = d_mnobj;
-    Mk.status = d_mstatus;
-    LC_HIP(ctx, extract_launch(ctx, K, h, w, mcfg, max_objects, Mk));
-    G.mask = d_mask;
-    LC_HIP(ctx, background_launch(ctx, K, h, w, bcfg, G));
-  }
-  ExVarArgs V;
-  V.K = K;
-  V.hw = hw;
-  V.sub = G.sub;
-  V.globalrms = G.globalrms;
-  V.exptime = d_exptime;
-  V.var = d_var;
-  hipLaunchKernelGGL(ex_variance_kernel, dim3((unsigned)std::min<size_t>((hw + kExThreads - 1) / kExThreads, 4096), (unsigned)std::min(K, 65535)),
-                     dim3(kExThreads), 0, ctx->stream, V);
-  LC_HIP(ctx, hipGetLastError());
-  B.data = G.sub;
-  B.var = d_var;
-  LC_HIP(ctx, extract_launch(ctx, K, h, w, ecfg, max_objects, B));
+  LC_HIP(ctx, import_launch(ctx, K, h, w, bcfg, ecfg, mask_sources_first, mcfg, max_objects, I));
   LC_HIP(ctx, call.stop());
   LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;

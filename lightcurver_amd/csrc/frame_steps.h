@@ -57,4 +57,26 @@ hipError_t extract_scratch(DeviceCall &call, int K, int h, int w, int max_object
 hipError_t extract_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg *cfg, int max_objects,
                           const ExtractBuffers &B);
 
+// ---- the import of frames (extract.hip): what lc_import_frames and lc_frames_import (cutout.hip) both run ------------
+
+struct ImportBuffers {
+  BackgroundBuffers G;  // data: the frames; sub, mesh_back, mesh_rms, globalback, globalrms are outputs of the import
+  ExtractBuffers B;     // objects, nobj, segmap (nullable), status are outputs; data and var are set by the launch
+  const float *exptime = nullptr;  // [K]
+  float *var = nullptr;            // [K][h][w] scratch
+  // scratch of mask_sources_first
+  uint8_t *mask = nullptr;                        // [K][h][w]
+  float *v0 = nullptr;                            // [K]
+  int32_t *mstatus = nullptr, *mnobj = nullptr;   // [K]
+};
+
+// The arguments of an import that both entries share: LC_OK, or the error code with ctx->err set ("<who>: ...").
+// pointers_ok: the entry's own test of the pointers it needs, reported with the other invalid arguments.
+int import_check(lc_ctx *ctx, const char *who, bool pointers_ok, int K, int h, int w, const float *exptime,
+                 const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg, int mask_sources_first,
+                 const lc_extract_cfg *mcfg, int max_objects);
+// every launch of lc_import_frames; the arguments have been checked
+hipError_t import_launch(lc_ctx *ctx, int K, int h, int w, const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg,
+                         int mask_sources_first, const lc_extract_cfg *mcfg, int max_objects, ImportBuffers &I);
+
 }  // namespace lc

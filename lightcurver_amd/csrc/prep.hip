@@ -14,6 +14,7 @@
 
 #include "device_call.h"
 #include "lc_common.h"
+#include "noise_pixel.h"
 #include "../../include/lcmi.h"
 
 namespace lc {
@@ -36,10 +37,7 @@ __device__ __forceinline__ void prep_pixel(const PrepArgs &A, int k, size_t idx,
   if (A.noisemap) {
     s = A.noisemap[idx];
   } else {
-    // electrons: data * t; back to electrons / second at the end (NaN data keeps the noise NaN, as in numpy)
-    const float e = d * t;
-    s = fmaxf(sqrtf(trms2 + fabsf(e)), 1e-7f) / t;
-    if (e != e) s = e;
+    s = noise_from_rms(d, t, trms2);
   }
   d /= inv_coef;
   s /= inv_coef;
@@ -58,8 +56,7 @@ __global__ __launch_bounds__(kPrepThreads) void prep_stamps_kernel(PrepArgs A) {
   const size_t base = (size_t)k * A.npix;
   const float inv_coef = A.coefficient ? A.coefficient[k] : 1.0f;  // the divisor itself: divisions are kept, as in the reference
   const float t = A.exptime ? A.exptime[k] : 1.0f;
-  const float trms = A.rms ? t * A.rms[k] : 0.f;
-  const float trms2 = trms * trms;
+  const float trms2 = A.rms ? noise_trms2(t, A.rms[k]) : 0.f;
   // pass 1: masked pixels of the stamp (flagged or NaN in both inputs), and whether anything is flagged
   int masked = 0, any = 0;
   for (int p = tid; p < A.npix; p += kPrepThreads) {

@@ -1,0 +1,147 @@
+"""A set of frames that stays on the device (``lc_frames``): uploaded once, imported where it lies, and the stamps of the
+ROI and of the stars cut from it later, once the caller has solved the astrometry.
+
+The reference imports a frame, writes the sky-subtracted frame to disk (lightcurver/processes/frame_importation.py:119)
+and cuts every stamp from it on the host, one ``Cutout2D`` at a time (cutout_making.py:23-51, from :188 and :238).  Here
+``FrameSet.import_frames`` is ``processes.frame_importation.import_frames`` on the resident planes, after which they hold
+the sky-subtracted frames, and ``FrameSet.cut_stamps`` cuts every stamp of one size, forms its noise map and masks it in
+one call (``lc_frames_cut_stamps``; DESIGN.md section 5 "Stamp cutting").  WCS and sky coordinates stay with the caller:
+positions are pixel positions as ``skycoord_to_pixel`` gives them, 0-based with the pixel centres at integers."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import f32, ptr
+
+_i32p = C.POINTER(C.c_int32)
+_u8p = C.POINTER(C.c_uint8)
+
+
+class FrameSet:
+    """K frames of one shape on the device.  ``stack``: (K, h, w), in electrons per second.  Raises without a device:
+    there is no CPU fallback."""
+
+    def __init__(self, stack, ctx=None):
+        d = f32(stack)
+        if d.ndim != 3 or 0 in d.shape:
+            raise ValueError(f'expected a (K, h, w) stack of frames, got {d.shape}')
+        self.ctx = ctx or _lib.default_context()
+        self._l = _lib.lib()
+        self.shape = d.shape
+        h = _lib.vp()
+        K, hh, ww = d.shape
+        self.ctx.check(self._l.lc_frames_create(self.ctx.h, K, hh, ww, ptr(d), C.byref(h)), 'lc_frames_create')
+        self.h = h
+
+    def __len__(self):
+        return self.shape[0]
+
+    @property
+    def frame_shape(self):
+        return self.shape[1:]
+
+    @property
+    def imported(self):
+        flag = C.c_int()
+        self.ctx.check(self._l.lc_frames_info(self._handle(), None, None, None, C.byref(flag)), 'lc_frames_info')
+        return bool(flag.value)
+
+    def _handle(self):
+        if not getattr(self, 'h', None):
+            raise _lib.LcError('the frame set has been closed')
+        return self.h
+
+    def import_frames(self, exptimes, n_boxes=10, mask_sources_first=False, detection_threshold=3, min_area=10,
+                      max_objects=8192, download_sub=False):
+        """``processes.frame_importation.import_frames`` on the resident planes, which hold ``sub`` afterwards; the same
+        dict, with ``sub`` None unless ``download_sub``.  Exposure times and background rms stay recorded for
+        ``cut_stamps``.  A set is imported once: a second call raises."""
+        from .processes.frame_importation import _import
+        handle = self._handle()
+
+        def call(*args):
+            self.ctx.check(self._l.lc_frames_import(handle, *args), 'lc_frames_import')
+
+        out = _import(call, self.shape, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area,
+                      max_objects, False, bool(download_sub))
+        if not download_sub:
+            del out['sub']
+        return out
+
+    def planes(self, first=0, count=None):
+        """The resident planes [first, first + count) as they are now: the frames as uploaded, or ``sub`` after the
+        import."""
+        K = self.shape[0]
+        first = int(first)
+        count = K - first if count is None else int(count)
+        out = np.empty((max(count, 0),) + self.shape[1:], np.float32)
+        self.ctx.check(self._l.lc_frames_get(self._handle(), first, count, ptr(out)), 'lc_frames_get')
+        return out
+
+    def cut_stamps(self, frame_index, positions_xy, size, exptimes=None, background_rms=None, do_mask_bad_columns=False,
+                   do_mask_cosmics=False, cosmics_masking_params=None):
+        """S stamps of ``size`` x ``size`` in one device call.  frame_index: (S,) or one frame for all; positions_xy:
+        (S, 2) pixel positions (x, y).  exptimes, background_rms: one per frame of the set, or one for all; after
+        ``import_frames`` both default to the recorded values.  Returns dict(data, noisemap (S, n, n) float32 with NaN
+        outside the frame, mask (S, n, n) bool as ``mask_cutout_batch`` gives it, origin (S, 2) int (x0, y0),
+        center_original (S, 2) float64 (x, y) of the part inside the frame, n_inside (S,), kernel_ms)."""
+        from .processes.cutout_making import _mask_settings, cutout_origin
+        handle = self._handle()
+        K, h, w = self.shape
+        n = int(size)
+        pos = np.asarray(positions_xy, np.float64).reshape(-1, 2)
+        S = len(pos)
+        if S < 1:
+            raise ValueError('cut_stamps: no position')
+        frame = np.ascontiguousarray(np.broadcast_to(np.asarray(frame_index, np.int32).reshape(-1), (S,)), dtype=np.int32)
+        if ((frame < 0) | (frame >= K)).any():
+            raise ValueError(f'cut_stamps: a frame index outside 0 .. {K - 1}')
+        origin, centre = cutout_origin(pos, n, (h, w))
+        x0 = np.ascontiguousarray(origin[:, 0], dtype=np.int32)
+        y0 = np.ascontiguousarray(origin[:, 1], dtype=np.int32)
+        masks = bool(do_mask_bad_columns or do_mask_cosmics)
+        if not self._l.lc_cutout_supported(n, int(masks)) or S * n * n >= 2 ** 31:
+            raise _lib.LcError(f'lc_frames_cut_stamps takes stamps of 8 .. 128 pixels with masks, any size with '
+                               f'S n n < 2^31 without, not {S} of {n}')
+        ccfg, bcfg = _mask_settings(dict(cosmics_masking_params or {}))
+
+        def per_frame(values):
+            if values is None:
+                return None
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(values, np.float32).reshape(-1), (K,)), dtype=np.float32)
+
+        t, rms = per_frame(exptimes), per_frame(background_rms)
+        if t is not None and not (np.isfinite(t) & (t > 0)).all():
+            raise ValueError('exposure times must be finite and > 0')
+        data = np.empty((S, n, n), np.float32)
+        noise = np.empty((S, n, n), np.float32)
+        mask = np.zeros((S, n, n), np.uint8)
+        inside = np.zeros(S, np.int32)
+        ms = C.c_float()
+        self.ctx.check(self._l.lc_frames_cut_stamps(
+            handle, S, n, frame.ctypes.data_as(_i32p), y0.ctypes.data_as(_i32p), x0.ctypes.data_as(_i32p), ptr(t), ptr(rms),
+            int(bool(do_mask_bad_columns)), int(bool(do_mask_cosmics)), C.byref(ccfg), C.byref(bcfg), ptr(data), ptr(noise),
+            mask.ctypes.data_as(_u8p), inside.ctypes.data_as(_i32p), C.byref(ms)), 'lc_frames_cut_stamps')
+        return dict(data=data, noisemap=noise, mask=mask.astype(bool), origin=origin, center_original=centre,
+                    n_inside=inside, kernel_ms=ms.value)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self._l.lc_frames_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        # (as Context.__del__: not while the interpreter shuts down)
+        try:
+            import sys
+            if not sys.is_finalizing():
+                self.close()
+        except Exception:
+            pass

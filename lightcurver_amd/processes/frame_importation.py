@@ -23,22 +23,35 @@ def import_frames(stack, exptimes, n_boxes=10, mask_sources_first=False, detecti
     if d.ndim != 3:
         raise ValueError(f'expected a (K, h, w) stack of frames, got {d.shape}')
     K, h, w = d.shape
+
+    def call(*args):
+        c = ctx or _lib.default_context()
+        c.check(_lib.lib().lc_import_frames(c.h, K, h, w, ptr(d), *args), 'lc_import_frames')
+
+    return _import(call, d.shape, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, max_objects,
+                   segmentation_map, True)
+
+
+def _import(call, shape, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, max_objects,
+            segmentation_map, with_sub):
+    """The settings, the outputs and the second run on a full object table, shared by ``import_frames`` and
+    ``FrameSet.import_frames``: ``call`` takes the arguments of ``lc_import_frames`` from ``exptime`` on."""
+    K, h, w = shape
     t = np.ascontiguousarray(np.broadcast_to(np.asarray(exptimes, np.float32).reshape(-1), (K,)), dtype=np.float32)
     if not (np.isfinite(t) & (t > 0)).all():
         raise ValueError('exposure times must be finite and > 0')
-    box = _box_size(d.shape, n_boxes)
-    sep._refuse(d.shape, box, box, 3, 3, 0.0)
+    box = _box_size(shape, n_boxes)
+    sep._refuse(shape, box, box, 3, 3, 0.0)
     if not sep.extract_supported(h, w):
         raise NotImplementedError(f'import_frames: {h} x {w} pixels is 2^31 or more')
     bcfg = _lib.BackgroundCfg(box, box, 3, 3, 0.0)
     ecfg = sep.extract_cfg(detection_threshold, min_area)
     mcfg = sep.extract_cfg(MASK_THRESH, MASK_MINAREA)
-    ctx = ctx or _lib.default_context()
     ny, nx = sep.mesh_shape(h, w, box, box)
-    out = dict(sub=np.empty(d.shape, np.float32), mesh_back=np.empty((K, ny, nx), np.float32),
+    out = dict(sub=np.empty(shape, np.float32) if with_sub else None, mesh_back=np.empty((K, ny, nx), np.float32),
                mesh_rms=np.empty((K, ny, nx), np.float32), globalback=np.empty(K, np.float32),
                globalrms=np.empty(K, np.float32), status=np.zeros(K, np.int32), nobj=np.zeros(K, np.int32),
-               ex_status=np.zeros(K, np.int32), segmap=np.zeros(d.shape, np.int32) if segmentation_map else None,
+               ex_status=np.zeros(K, np.int32), segmap=np.zeros(shape, np.int32) if segmentation_map else None,
                objects=[], box=box, kernel_ms=0.0)
     if not K:
         return out
@@ -46,12 +59,11 @@ def import_frames(stack, exptimes, n_boxes=10, mask_sources_first=False, detecti
     for attempt in range(2):
         table = np.zeros((K, cap), _lib.EXTRACT_OBJECT_DTYPE)
         ms = C.c_float()
-        ctx.check(_lib.lib().lc_import_frames(
-            ctx.h, K, h, w, ptr(d), ptr(t), C.byref(bcfg), C.byref(ecfg), int(bool(mask_sources_first)), C.byref(mcfg), cap,
-            ptr(out['sub']), ptr(out['mesh_back']), ptr(out['mesh_rms']), ptr(out['globalback']), ptr(out['globalrms']),
-            out['status'].ctypes.data_as(_i32p), table.ctypes.data_as(C.c_void_p), out['nobj'].ctypes.data_as(_i32p),
-            out['segmap'].ctypes.data_as(_i32p) if segmentation_map else None, out['ex_status'].ctypes.data_as(_i32p),
-            C.byref(ms)), 'lc_import_frames')
+        call(ptr(t), C.byref(bcfg), C.byref(ecfg), int(bool(mask_sources_first)), C.byref(mcfg), cap,
+             ptr(out['sub']), ptr(out['mesh_back']), ptr(out['mesh_rms']), ptr(out['globalback']), ptr(out['globalrms']),
+             out['status'].ctypes.data_as(_i32p), table.ctypes.data_as(C.c_void_p), out['nobj'].ctypes.data_as(_i32p),
+             out['segmap'].ctypes.data_as(_i32p) if segmentation_map else None, out['ex_status'].ctypes.data_as(_i32p),
+             C.byref(ms))
         out['kernel_ms'] += ms.value
         if not (out['ex_status'] == 1).any():
             break

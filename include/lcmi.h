@@ -253,6 +253,32 @@ int lc_extract_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const
                       lc_extract_object *objects /*nullable*/, int32_t *nobj /*[K]*/, int32_t *segmap /*nullable*/,
                       uint8_t *mask /*nullable*/, int32_t *status /*[K]*/, float *kernel_ms /*nullable*/);
 
+/* ---- the same with sep's de-blending and cleaning: sep.extract as the reference calls it --------------------
+ * DESIGN.md section 5 "De-blending and cleaning of frame objects".  The parents are the objects of lc_extract_frames.  A
+ * parent whose box has both sides <= 64 pixels and that is not flagged RANGE is de-blended inside its box by the tree of
+ * lc_segment_stamps (deblend_nthresh levels, the contrast deblend_cont, at most LC_SEGMENT_MAX_OBJECTS leaves and 64 tree
+ * nodes per parent); its leaves are objects whatever their size.  A parent with a larger box, or one that exceeds a
+ * capacity, stays whole and carries flag bit 8 (LC_EXTRACT_FLAG_NODEBLEND); the frame's status is not affected.  With
+ * clean != 0 every object is then merged into the brighter neighbour whose Moffat wing exceeds it (sep's clean with
+ * clean_param 1), chains followed to their ends.  The final objects are numbered in the raster order of their first
+ * pixels and measured as in lc_extract_frames; segmap and mask follow that numbering.  With deblend_cont >= 1 and
+ * clean = 0 everything but flag bit 8 equals lc_extract_frames bit for bit.
+ *   Arguments, outputs, status and error codes as lc_extract_frames.  LC_ERR_UNSUPPORTED also for clean_param != 1 and a
+ *   deblend_nthresh other than 4, 8, 16 or 32; LC_ERR_INVALID also for a deblend_cont that is negative or not finite and
+ *   a missing dcfg.  The call waits for the device twice before its last launch, to size its tables. */
+#define LC_EXTRACT_FLAG_NODEBLEND 8
+typedef struct {
+  int32_t deblend_nthresh; /* sep: 32; 4, 8, 16 or 32 */
+  float deblend_cont;      /* sep: 0.005; >= 1: no de-blending */
+  int32_t clean;           /* sep: 1 */
+  float clean_param;       /* sep: 1.0, the only one built */
+} lc_deblend_cfg;
+int lc_extract_frames_deblended(lc_ctx *ctx, int K, int h, int w, const float *data, const float *var /*nullable*/,
+                                const float *var_scalar /*[K], read when var is null*/, const lc_extract_cfg *cfg,
+                                const lc_deblend_cfg *dcfg, int max_objects, lc_extract_object *objects /*nullable*/,
+                                int32_t *nobj /*[K]*/, int32_t *segmap /*nullable*/, uint8_t *mask /*nullable*/,
+                                int32_t *status /*[K]*/, float *kernel_ms /*nullable*/);
+
 /* ---- the arithmetic of importing a frame, with the frame uploaded once -----------------------------------
  * Reference: lightcurver/processes/frame_importation.py:81-141.  data [K][h][w] in electrons per second, exptime [K].
  *   1. the sky background as lc_background_frames (bcfg);
@@ -269,6 +295,14 @@ int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const 
                      float *mesh_back /*nullable*/, float *mesh_rms /*nullable*/, float *globalback, float *globalrms,
                      int32_t *bg_status /*nullable*/, lc_extract_object *objects, int32_t *nobj,
                      int32_t *segmap /*nullable*/, int32_t *ex_status, float *kernel_ms /*nullable*/);
+/* The same with step 4 as lc_extract_frames_deblended (dcfg); the source mask of step 2 is never de-blended. */
+int lc_import_frames_deblended(lc_ctx *ctx, int K, int h, int w, const float *data, const float *exptime /*[K]*/,
+                               const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg, const lc_deblend_cfg *dcfg,
+                               int mask_sources_first, const lc_extract_cfg *mcfg /*read when mask_sources_first*/,
+                               int max_objects, float *sub, float *mesh_back /*nullable*/, float *mesh_rms /*nullable*/,
+                               float *globalback, float *globalrms, int32_t *bg_status /*nullable*/,
+                               lc_extract_object *objects, int32_t *nobj, int32_t *segmap /*nullable*/,
+                               int32_t *ex_status, float *kernel_ms /*nullable*/);
 
 /* ---- a frame set that stays on the device, and the stamps cut from it -----------------------------------------
  * Reference: lightcurver/processes/cutout_making.py:23-51 (extract_stamp: Cutout2D(mode='partial', fill_value=nan) and the
@@ -305,6 +339,14 @@ int lc_frames_import(lc_frames *f, const float *exptime /*[K]*/, const lc_backgr
                      float *sub /*nullable*/, float *mesh_back /*nullable*/, float *mesh_rms /*nullable*/, float *globalback,
                      float *globalrms, int32_t *bg_status /*nullable*/, lc_extract_object *objects, int32_t *nobj,
                      int32_t *segmap /*nullable*/, int32_t *ex_status, float *kernel_ms /*nullable*/);
+/* lc_frames_import with the catalogue as lc_extract_frames_deblended (dcfg) */
+int lc_frames_import_deblended(lc_frames *f, const float *exptime /*[K]*/, const lc_background_cfg *bcfg,
+                               const lc_extract_cfg *ecfg, const lc_deblend_cfg *dcfg, int mask_sources_first,
+                               const lc_extract_cfg *mcfg /*read when mask_sources_first*/, int max_objects,
+                               float *sub /*nullable*/, float *mesh_back /*nullable*/, float *mesh_rms /*nullable*/,
+                               float *globalback, float *globalrms, int32_t *bg_status /*nullable*/,
+                               lc_extract_object *objects, int32_t *nobj, int32_t *segmap /*nullable*/,
+                               int32_t *ex_status, float *kernel_ms /*nullable*/);
 int lc_cutout_supported(int n, int with_masks);
 int lc_frames_cut_stamps(lc_frames *f, int S, int n, const int32_t *frame /*[S]*/, const int32_t *y0 /*[S]*/,
                          const int32_t *x0 /*[S]*/, const float *exptime /*[K], nullable after an import*/,

@@ -68,6 +68,11 @@ class ExtractCfg(C.Structure):
     _fields_ = [('thresh', C.c_float), ('minarea', C.c_int32), ('filter', C.c_int32)]
 
 
+class DeblendCfg(C.Structure):
+    _fields_ = [('deblend_nthresh', C.c_int32), ('deblend_cont', C.c_float), ('clean', C.c_int32),
+                ('clean_param', C.c_float)]
+
+
 class ExtractObject(C.Structure):
     _fields_ = [('first', C.c_int32), ('npix', C.c_int32), ('xmin', C.c_int32), ('xmax', C.c_int32), ('ymin', C.c_int32),
                 ('ymax', C.c_int32), ('xpeak', C.c_int32), ('ypeak', C.c_int32), ('flag', C.c_int32), ('pad', C.c_int32),
@@ -113,6 +118,15 @@ SIGNATURES = {
     'lc_extract_supported': (C.c_int, [C.c_int, C.c_int]),
     'lc_extract_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(ExtractCfg), C.c_int, vp, ip, ip,
                                     C.POINTER(C.c_uint8), ip, C.POINTER(C.c_float)]),
+    'lc_extract_frames_deblended': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(ExtractCfg),
+                                              C.POINTER(DeblendCfg), C.c_int, vp, ip, ip, C.POINTER(C.c_uint8), ip,
+                                              C.POINTER(C.c_float)]),
+    'lc_import_frames_deblended': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(BackgroundCfg),
+                                             C.POINTER(ExtractCfg), C.POINTER(DeblendCfg), C.c_int, C.POINTER(ExtractCfg),
+                                             C.c_int, fp, fp, fp, fp, fp, ip, vp, ip, ip, ip, C.POINTER(C.c_float)]),
+    'lc_frames_import_deblended': (C.c_int, [vp, fp, C.POINTER(BackgroundCfg), C.POINTER(ExtractCfg), C.POINTER(DeblendCfg),
+                                             C.c_int, C.POINTER(ExtractCfg), C.c_int, fp, fp, fp, fp, fp, ip, vp, ip, ip, ip,
+                                             C.POINTER(C.c_float)]),
     'lc_import_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(BackgroundCfg), C.POINTER(ExtractCfg),
                                    C.c_int, C.POINTER(ExtractCfg), C.c_int, fp, fp, fp, fp, fp, ip, vp, ip, ip, ip,
                                    C.POINTER(C.c_float)]),

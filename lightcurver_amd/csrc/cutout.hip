@@ -157,18 +157,25 @@ int lc_frames_get(lc_frames *f, int first, int count, float *out) {
   return LC_OK;
 }
 
-int lc_frames_import(lc_frames *f, const float *exptime, const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg,
-                     int mask_sources_first, const lc_extract_cfg *mcfg, int max_objects, float *sub, float *mesh_back,
-                     float *mesh_rms, float *globalback, float *globalrms, int32_t *bg_status, lc_extract_object *objects,
-                     int32_t *nobj, int32_t *segmap, int32_t *ex_status, float *kernel_ms) {
+}  // extern "C"
+
+// lc_frames_import (dcfg not read) and lc_frames_import_deblended
+static int frames_import(const char *who, bool deblended, lc_frames *f, const float *exptime, const lc_background_cfg *bcfg,
+                         const lc_extract_cfg *ecfg, const lc_deblend_cfg *dcfg, int mask_sources_first,
+                         const lc_extract_cfg *mcfg, int max_objects, float *sub, float *mesh_back, float *mesh_rms,
+                         float *globalback, float *globalrms, int32_t *bg_status, lc_extract_object *objects, int32_t *nobj,
+                         int32_t *segmap, int32_t *ex_status, float *kernel_ms) {
   if (!f) return LC_ERR_INVALID;
   lc_ctx *ctx = f->ctx;
   const int K = f->K, h = f->h, w = f->w;
-  if (f->imported) LC_FAIL(ctx, LC_ERR_INVALID, "lc_frames_import: the frame set has been imported already");
+  if (f->imported) LC_FAIL(ctx, LC_ERR_INVALID, std::string(who) + ": the frame set has been imported already");
   const bool pointers_ok = globalback && globalrms && objects && nobj && ex_status;
-  if (int rc = import_check(ctx, "lc_frames_import", pointers_ok, K, h, w, exptime, bcfg, ecfg, mask_sources_first, mcfg,
-                            max_objects))
+  if (int rc = import_check(ctx, who, pointers_ok, K, h, w, exptime, bcfg, ecfg, mask_sources_first, mcfg, max_objects))
     return rc;
+  if (deblended) {
+    int code = 0;
+    if (const char *why = deblend_cfg_error(dcfg, &code)) LC_FAIL(ctx, code, std::string(who) + ": " + why);
+  }
   LC_ENTER(ctx);
   const size_t hw = (size_t)h * w, tot = (size_t)K * hw, meshes = (size_t)K * background_meshes(h, w, bcfg->bw, bcfg->bh);
   const std::vector<double> pivots = background_pivots();
@@ -204,6 +211,8 @@ int lc_frames_import(lc_frames *f, const float *exptime, const lc_background_cfg
     LC_HIP(ctx, call.alloc((size_t)K, &I.mstatus));
     LC_HIP(ctx, call.alloc((size_t)K, &I.mnobj));
   }
+  I.dcfg = deblended ? dcfg : nullptr;
+  I.call = &call;
   LC_HIP(ctx, call.start());
   LC_HIP(ctx, import_launch(ctx, K, h, w, bcfg, ecfg, mask_sources_first, mcfg, max_objects, I));
   LC_HIP(ctx, call.stop());
@@ -215,6 +224,26 @@ int lc_frames_import(lc_frames *f, const float *exptime, const lc_background_cfg
   f->sub = nullptr;
   f->imported = true;
   return LC_OK;
+}
+
+extern "C" {
+
+int lc_frames_import(lc_frames *f, const float *exptime, const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg,
+                     int mask_sources_first, const lc_extract_cfg *mcfg, int max_objects, float *sub, float *mesh_back,
+                     float *mesh_rms, float *globalback, float *globalrms, int32_t *bg_status, lc_extract_object *objects,
+                     int32_t *nobj, int32_t *segmap, int32_t *ex_status, float *kernel_ms) {
+  return frames_import("lc_frames_import", false, f, exptime, bcfg, ecfg, nullptr, mask_sources_first, mcfg, max_objects, sub,
+                       mesh_back, mesh_rms, globalback, globalrms, bg_status, objects, nobj, segmap, ex_status, kernel_ms);
+}
+
+int lc_frames_import_deblended(lc_frames *f, const float *exptime, const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg,
+                               const lc_deblend_cfg *dcfg, int mask_sources_first, const lc_extract_cfg *mcfg,
+                               int max_objects, float *sub, float *mesh_back, float *mesh_rms, float *globalback,
+                               float *globalrms, int32_t *bg_status, lc_extract_object *objects, int32_t *nobj,
+                               int32_t *segmap, int32_t *ex_status, float *kernel_ms) {
+  return frames_import("lc_frames_import_deblended", true, f, exptime, bcfg, ecfg, dcfg, mask_sources_first, mcfg,
+                       max_objects, sub, mesh_back, mesh_rms, globalback, globalrms, bg_status, objects, nobj, segmap,
+                       ex_status, kernel_ms);
 }
 
 int lc_cutout_supported(int n, int with_masks) {

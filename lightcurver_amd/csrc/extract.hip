@@ -11,7 +11,7 @@
 //   ex_count_kernel, ex_scan_kernel, ex_number_kernel
 //                      the roots with at least minarea pixels, counted per block of 256 pixels, scanned per frame and
 //                      numbered in raster order: the root's count becomes its object number;
-//   ex_box_kernel      segmap and mask, and the bounding boxes by integer atomicMin / atomicMax per run;
+//   ex_box_kernel      segmap and mask, and the bounding boxes by integer atomicMin / atomicMax per run of one object;
 //   ex_measure_kernel  one workgroup per object over its box: integer moments, peaks and the flux in a fixed order.
 // Labels only ever decrease (a pixel points at a pixel before it in raster order), so every find terminates; the loops
 // carry a bound all the same, and reaching it sets the frame's status to 2.  Offsets into the planes are 64-bit.
@@ -409,8 +409,19 @@ struct ExBoxArgs {
   uint8_t *mask;
 };
 
+// The same for runs of one object number: after de-blending (deblend.hip) two objects can touch within a line.  Without
+// it a detected pixel and its detected neighbour belong to one component, and these runs are those of ex_run.
+__device__ __forceinline__ int ex_run_of(const int *s_num, int tid, int x, int w, int left_in_block) {
+  const int num = s_num[tid];
+  if (num <= 0 || (tid > 0 && x > 0 && s_num[tid - 1] == num)) return 0;
+  const int room = min(left_in_block, w - x);
+  int len = 1;
+  while (len < room && s_num[tid + len] == num) ++len;
+  return len;
+}
+
 __global__ __launch_bounds__(kExThreads) void ex_box_kernel(ExBoxArgs A) {
-  __shared__ uint8_t s_set[kExThreads];
+  __shared__ int s_num[kExThreads];
   const ExGeom g = A.g;
   const int tid = threadIdx.x;
   const unsigned frame = blockIdx.x / g.nblk, b = blockIdx.x - frame * g.nblk;
@@ -424,12 +435,12 @@ __global__ __launch_bounds__(kExThreads) void ex_box_kernel(ExBoxArgs A) {
     if (A.segmap) A.segmap[base + p64] = num;
     if (A.mask) A.mask[base + p64] = num > 0;
   }
-  s_set[tid] = num > 0;
+  s_num[tid] = num;
   __syncthreads();
   if (num > 0 && num <= A.max_objects && A.aux) {
     const int p = (int)p64, y = p / g.w, x = p - y * g.w;
     const int left = (int)min((long long)(kExThreads - tid), (long long)g.hw - p64);
-    const int len = ex_run(s_set, tid, x, g.w, left);
+    const int len = ex_run_of(s_num, tid, x, g.w, left);
     if (len > 0) {
       int32_t *a = A.aux + ((size_t)frame * A.max_objects + (num - 1)) * kExAux;
       atomicMin(a + 2, x);
@@ -649,16 +660,13 @@ hipError_t extract_scratch(DeviceCall &call, int K, int h, int w, int max_object
   return e;
 }
 
-hipError_t extract_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg *cfg, int max_objects,
-                          const ExtractBuffers &B) {
+hipError_t extract_label_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg *cfg, const ExtractBuffers &B) {
   ExGeom g;
   if (!ex_geom(h, w, &g)) return hipErrorInvalidValue;
   const size_t tot = (size_t)K * g.hw;
-  const bool table = B.objects != nullptr;
   hipStream_t st = ctx->stream;
   hipError_t e = hipMemsetAsync(B.count, 0, tot * sizeof(int32_t), st);
   if (e == hipSuccess) e = hipMemsetAsync(B.status, 0, (size_t)K * sizeof(int32_t), st);
-  if (e == hipSuccess && table) e = hipMemsetAsync(B.objects, 0, (size_t)K * max_objects * sizeof(lc_extract_object), st);
   if (e != hipSuccess) return e;
   const unsigned tiles = (unsigned)K * (unsigned)(g.tx * g.ty), blocks = (unsigned)K * g.nblk;
 
@@ -688,38 +696,57 @@ hipError_t extract_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg
   F.count = B.count;
   F.status = B.status;
   hipLaunchKernelGGL(ex_flatten_kernel, dim3(blocks), dim3(kExThreads), 0, st, F);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return hipGetLastError();
+}
 
+static ExNumberArgs ex_number_args(const ExGeom &g, int minarea, int max_objects, const ExtractBuffers &B) {
   ExNumberArgs N;
   N.g = g;
-  N.minarea = cfg->minarea;
+  N.minarea = minarea;
   N.max_objects = max_objects;
   N.label = B.label;
   N.count = B.count;
   N.block = B.block;
   N.status = B.status;
   N.nobj = B.nobj;
-  N.aux = table ? B.aux : nullptr;
-  hipLaunchKernelGGL(ex_count_kernel, dim3(blocks), dim3(kExThreads), 0, st, N);
+  N.aux = B.aux;
+  return N;
+}
+
+hipError_t extract_count_launch(lc_ctx *ctx, int K, int h, int w, int minarea, int max_objects, const ExtractBuffers &B) {
+  ExGeom g;
+  if (!ex_geom(h, w, &g)) return hipErrorInvalidValue;
+  const ExNumberArgs N = ex_number_args(g, minarea, max_objects, B);
+  hipError_t e;
+  hipLaunchKernelGGL(ex_count_kernel, dim3((unsigned)K * g.nblk), dim3(kExThreads), 0, ctx->stream, N);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(ex_scan_kernel, dim3((unsigned)K), dim3(kExThreads), 0, st, N);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(ex_scan_kernel, dim3((unsigned)K), dim3(kExThreads), 0, ctx->stream, N);
+  return hipGetLastError();
+}
+
+hipError_t extract_table_launch(lc_ctx *ctx, int K, int h, int w, int minarea, int max_objects, const ExtractBuffers &B) {
+  ExGeom g;
+  if (!ex_geom(h, w, &g)) return hipErrorInvalidValue;
+  hipStream_t st = ctx->stream;
+  const unsigned blocks = (unsigned)K * g.nblk;
+  const ExNumberArgs N = ex_number_args(g, minarea, max_objects, B);
+  hipError_t e;
   hipLaunchKernelGGL(ex_number_kernel, dim3(blocks), dim3(kExThreads), 0, st, N);
   if ((e = hipGetLastError()) != hipSuccess) return e;
 
-  if (table || B.segmap || B.mask) {
+  if (B.aux || B.segmap || B.mask) {
     ExBoxArgs X;
     X.g = g;
     X.max_objects = max_objects;
     X.label = B.label;
     X.count = B.count;
-    X.aux = N.aux;
+    X.aux = B.aux;
     X.segmap = B.segmap;
     X.mask = B.mask;
     hipLaunchKernelGGL(ex_box_kernel, dim3(blocks), dim3(kExThreads), 0, st, X);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  if (table) {
+  if (B.objects) {
     ExMeasureArgs Q;
     Q.g = g;
     Q.K = K;
@@ -738,7 +765,19 @@ hipError_t extract_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg
   return hipSuccess;
 }
 
-static const char *ex_cfg_error(const lc_extract_cfg *c) {
+hipError_t extract_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg *cfg, int max_objects,
+                          const ExtractBuffers &B0) {
+  ExtractBuffers B = B0;
+  if (!B.objects) B.aux = nullptr;  // the boxes are made for the table alone
+  hipError_t e = hipSuccess;
+  if (B.objects) e = hipMemsetAsync(B.objects, 0, (size_t)K * max_objects * sizeof(lc_extract_object), ctx->stream);
+  if (e == hipSuccess) e = extract_label_launch(ctx, K, h, w, cfg, B);
+  if (e == hipSuccess) e = extract_count_launch(ctx, K, h, w, cfg->minarea, max_objects, B);
+  if (e == hipSuccess) e = extract_table_launch(ctx, K, h, w, cfg->minarea, max_objects, B);
+  return e;
+}
+
+const char *extract_cfg_error(const lc_extract_cfg *c) {
   if (!c) return "a missing configuration";
   if (!std::isfinite(c->thresh) || !(c->thresh > 0.0f)) return "thresh must be finite and > 0";
   if (c->minarea < 1) return "minarea < 1";
@@ -756,9 +795,9 @@ int import_check(lc_ctx *ctx, const char *who, bool pointers_ok, int K, int h, i
   for (int k = 0; k < K; ++k)
     if (!std::isfinite(exptime[k]) || !(exptime[k] > 0.0f))
       LC_FAIL(ctx, LC_ERR_INVALID, me + ": an exposure time that is not finite or not > 0");
-  if (const char *why = ex_cfg_error(ecfg)) LC_FAIL(ctx, LC_ERR_INVALID, me + ": catalogue: " + why);
+  if (const char *why = extract_cfg_error(ecfg)) LC_FAIL(ctx, LC_ERR_INVALID, me + ": catalogue: " + why);
   if (mask_sources_first)
-    if (const char *why = ex_cfg_error(mcfg)) LC_FAIL(ctx, LC_ERR_INVALID, me + ": source mask: " + why);
+    if (const char *why = extract_cfg_error(mcfg)) LC_FAIL(ctx, LC_ERR_INVALID, me + ": source mask: " + why);
   if (bcfg->fthresh != 0.0f) LC_FAIL(ctx, LC_ERR_UNSUPPORTED, me + ": fthresh other than 0 is not built");
   if (!lc_background_supported(h, w, bcfg->bw, bcfg->bh, bcfg->fw, bcfg->fh) ||
       !background_batch_fits(K, h, w, bcfg->bw, bcfg->bh))
@@ -805,6 +844,7 @@ hipError_t import_launch(lc_ctx *ctx, int K, int h, int w, const lc_background_c
   if ((e = hipGetLastError()) != hipSuccess) return e;
   B.data = G.sub;
   B.var = I.var;
+  if (I.dcfg) return deblend_launch(ctx, *I.call, K, h, w, ecfg, I.dcfg, max_objects, B);
   return extract_launch(ctx, K, h, w, ecfg, max_objects, B);
 }
 
@@ -825,7 +865,7 @@ int lc_extract_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const
   if (!ctx) return LC_ERR_INVALID;
   if (K < 1 || h < 1 || w < 1 || !data || (!var && !var_scalar) || !nobj || !status || max_objects < 1)
     LC_FAIL(ctx, LC_ERR_INVALID, "lc_extract_frames: invalid argument");
-  if (const char *why = ex_cfg_error(cfg)) LC_FAIL(ctx, LC_ERR_INVALID, std::string("lc_extract_frames: ") + why);
+  if (const char *why = extract_cfg_error(cfg)) LC_FAIL(ctx, LC_ERR_INVALID, std::string("lc_extract_frames: ") + why);
   if (!lc_extract_supported(h, w) || !extract_batch_fits(K, h, w) ||
       (int64_t)K * max_objects >= ((int64_t)1 << 31) / kExAux)
     LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_extract_frames: frames of 2^31 pixels or more, or more of them than one grid takes");
@@ -849,16 +889,23 @@ int lc_extract_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const
   return LC_OK;
 }
 
-int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const float *exptime,
-                     const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg, int mask_sources_first,
-                     const lc_extract_cfg *mcfg, int max_objects, float *sub, float *mesh_back, float *mesh_rms,
-                     float *globalback, float *globalrms, int32_t *bg_status, lc_extract_object *objects, int32_t *nobj,
-                     int32_t *segmap, int32_t *ex_status, float *kernel_ms) {
+}  // extern "C"
+
+// lc_import_frames (dcfg null) and lc_import_frames_deblended
+static int import_frames(const char *who, bool deblended, lc_ctx *ctx, int K, int h, int w, const float *data,
+                         const float *exptime, const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg,
+                         const lc_deblend_cfg *dcfg, int mask_sources_first, const lc_extract_cfg *mcfg, int max_objects,
+                         float *sub, float *mesh_back, float *mesh_rms, float *globalback, float *globalrms,
+                         int32_t *bg_status, lc_extract_object *objects, int32_t *nobj, int32_t *segmap, int32_t *ex_status,
+                         float *kernel_ms) {
   if (!ctx) return LC_ERR_INVALID;
   const bool pointers_ok = data && sub && globalback && globalrms && objects && nobj && ex_status;
-  if (int rc = import_check(ctx, "lc_import_frames", pointers_ok, K, h, w, exptime, bcfg, ecfg, mask_sources_first, mcfg,
-                            max_objects))
+  if (int rc = import_check(ctx, who, pointers_ok, K, h, w, exptime, bcfg, ecfg, mask_sources_first, mcfg, max_objects))
     return rc;
+  if (deblended) {
+    int code = 0;
+    if (const char *why = deblend_cfg_error(dcfg, &code)) LC_FAIL(ctx, code, std::string(who) + ": " + why);
+  }
   LC_ENTER(ctx);
   const size_t hw = (size_t)h * w, tot = (size_t)K * hw, meshes = (size_t)K * background_meshes(h, w, bcfg->bw, bcfg->bh);
   const std::vector<double> pivots = background_pivots();
@@ -890,11 +937,36 @@ int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const 
     LC_HIP(ctx, call.alloc((size_t)K, &I.mstatus));
     LC_HIP(ctx, call.alloc((size_t)K, &I.mnobj));
   }
+  I.dcfg = deblended ? dcfg : nullptr;
+  I.call = &call;
   LC_HIP(ctx, call.start());
   LC_HIP(ctx, import_launch(ctx, K, h, w, bcfg, ecfg, mask_sources_first, mcfg, max_objects, I));
   LC_HIP(ctx, call.stop());
   LC_HIP(ctx, call.finish(kernel_ms));
   return LC_OK;
+}
+
+extern "C" {
+
+int lc_import_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const float *exptime,
+                     const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg, int mask_sources_first,
+                     const lc_extract_cfg *mcfg, int max_objects, float *sub, float *mesh_back, float *mesh_rms,
+                     float *globalback, float *globalrms, int32_t *bg_status, lc_extract_object *objects, int32_t *nobj,
+                     int32_t *segmap, int32_t *ex_status, float *kernel_ms) {
+  return import_frames("lc_import_frames", false, ctx, K, h, w, data, exptime, bcfg, ecfg, nullptr, mask_sources_first, mcfg,
+                       max_objects, sub, mesh_back, mesh_rms, globalback, globalrms, bg_status, objects, nobj, segmap,
+                       ex_status, kernel_ms);
+}
+
+int lc_import_frames_deblended(lc_ctx *ctx, int K, int h, int w, const float *data, const float *exptime,
+                               const lc_background_cfg *bcfg, const lc_extract_cfg *ecfg, const lc_deblend_cfg *dcfg,
+                               int mask_sources_first, const lc_extract_cfg *mcfg, int max_objects, float *sub,
+                               float *mesh_back, float *mesh_rms, float *globalback, float *globalrms, int32_t *bg_status,
+                               lc_extract_object *objects, int32_t *nobj, int32_t *segmap, int32_t *ex_status,
+                               float *kernel_ms) {
+  return import_frames("lc_import_frames_deblended", true, ctx, K, h, w, data, exptime, bcfg, ecfg, dcfg, mask_sources_first,
+                       mcfg, max_objects, sub, mesh_back, mesh_rms, globalback, globalrms, bg_status, objects, nobj, segmap,
+                       ex_status, kernel_ms);
 }
 
 }  // extern "C"

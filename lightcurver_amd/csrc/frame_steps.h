@@ -56,6 +56,25 @@ hipError_t extract_scratch(DeviceCall &call, int K, int h, int w, int max_object
 // every launch of lc_extract_frames; the arguments have been checked
 hipError_t extract_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg *cfg, int max_objects,
                           const ExtractBuffers &B);
+// Its launches in three parts, which the de-blended extraction (deblend.hip) runs more than once on planes it rewrote:
+//   label: count and status zeroed, then snr, the label plane of roots and count[root] = pixels of the component;
+//   count: nobj [K] = the roots with count >= minarea (status 1 where nobj > max_objects);
+//   table: count[root] becomes the object number, aux (where not null), segmap, mask, and objects (where not null).
+hipError_t extract_label_launch(lc_ctx *ctx, int K, int h, int w, const lc_extract_cfg *cfg, const ExtractBuffers &B);
+hipError_t extract_count_launch(lc_ctx *ctx, int K, int h, int w, int minarea, int max_objects, const ExtractBuffers &B);
+hipError_t extract_table_launch(lc_ctx *ctx, int K, int h, int w, int minarea, int max_objects, const ExtractBuffers &B);
+// what is wrong with the settings, or null
+const char *extract_cfg_error(const lc_extract_cfg *cfg);
+
+// ---- de-blending and cleaning of frame objects (deblend.hip) --------------------------------------------------------
+
+// what is wrong with the settings (*code: the error code), or null
+const char *deblend_cfg_error(const lc_deblend_cfg *dcfg, int *code);
+// Every launch of lc_extract_frames_deblended; the arguments have been checked.  Unlike extract_launch it waits for the
+// stream twice, to size the tables of the parents and of the final objects from their counts, and takes those tables
+// from the call's pool.
+hipError_t deblend_launch(lc_ctx *ctx, DeviceCall &call, int K, int h, int w, const lc_extract_cfg *cfg,
+                          const lc_deblend_cfg *dcfg, int max_objects, const ExtractBuffers &B);
 
 // ---- the import of frames (extract.hip): what lc_import_frames and lc_frames_import (cutout.hip) both run ------------
 
@@ -68,6 +87,9 @@ struct ImportBuffers {
   uint8_t *mask = nullptr;                        // [K][h][w]
   float *v0 = nullptr;                            // [K]
   int32_t *mstatus = nullptr, *mnobj = nullptr;   // [K]
+  // the catalogue de-blended and cleaned (null: not), with the call that owns its tables
+  const lc_deblend_cfg *dcfg = nullptr;
+  DeviceCall *call = nullptr;
 };
 
 // The arguments of an import that both entries share: LC_OK, or the error code with ctx->err set ("<who>: ...").

@@ -53,18 +53,20 @@ class FrameSet:
         return self.h
 
     def import_frames(self, exptimes, n_boxes=10, mask_sources_first=False, detection_threshold=3, min_area=10,
-                      max_objects=8192, download_sub=False):
+                      max_objects=8192, download_sub=False, deblend=False):
         """``processes.frame_importation.import_frames`` on the resident planes, which hold ``sub`` afterwards; the same
-        dict, with ``sub`` None unless ``download_sub``.  Exposure times and background rms stay recorded for
+        dict, with ``sub`` None unless ``download_sub``.  ``deblend``: as there (``lc_frames_import_deblended``).  Exposure times and background rms stay recorded for
         ``cut_stamps``.  A set is imported once: a second call raises."""
+        from . import sep
         from .processes.frame_importation import _import
         handle = self._handle()
+        name = 'lc_frames_import_deblended' if sep.deblend_cfg(deblend) is not None else 'lc_frames_import'
 
         def call(*args):
-            self.ctx.check(self._l.lc_frames_import(handle, *args), 'lc_frames_import')
+            self.ctx.check(getattr(self._l, name)(handle, *args), name)
 
         out = _import(call, self.shape, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area,
-                      max_objects, False, bool(download_sub))
+                      max_objects, False, bool(download_sub), deblend)
         if not download_sub:
             del out['sub']
         return out

@@ -15,8 +15,9 @@ _i32p = C.POINTER(C.c_int32)
 
 
 def import_frames(stack, exptimes, n_boxes=10, mask_sources_first=False, detection_threshold=3, min_area=10,
-                  max_objects=8192, segmentation_map=False, ctx=None):
-    """One ``lc_import_frames`` call over a (K, h, w) stack.  Returns dict(sub (K, h, w), mesh_back, mesh_rms, globalback,
+                  max_objects=8192, segmentation_map=False, ctx=None, deblend=False):
+    """One ``lc_import_frames`` call over a (K, h, w) stack; with ``deblend`` (True: sep's defaults, the reference's
+    call; or a dict as ``sep.extract_frames`` takes) one ``lc_import_frames_deblended`` call.  Returns dict(sub (K, h, w), mesh_back, mesh_rms, globalback,
     globalrms, status (the background's), objects: list of K record arrays, nobj, ex_status, segmap (if asked), box,
     kernel_ms).  A frame with more than ``max_objects`` objects makes the call run once more with the largest count."""
     d = f32(stack)
@@ -24,18 +25,21 @@ def import_frames(stack, exptimes, n_boxes=10, mask_sources_first=False, detecti
         raise ValueError(f'expected a (K, h, w) stack of frames, got {d.shape}')
     K, h, w = d.shape
 
+    name = 'lc_import_frames_deblended' if sep.deblend_cfg(deblend) is not None else 'lc_import_frames'
+
     def call(*args):
         c = ctx or _lib.default_context()
-        c.check(_lib.lib().lc_import_frames(c.h, K, h, w, ptr(d), *args), 'lc_import_frames')
+        c.check(getattr(_lib.lib(), name)(c.h, K, h, w, ptr(d), *args), name)
 
     return _import(call, d.shape, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, max_objects,
-                   segmentation_map, True)
+                   segmentation_map, True, deblend)
 
 
 def _import(call, shape, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, max_objects,
-            segmentation_map, with_sub):
+            segmentation_map, with_sub, deblend=False):
     """The settings, the outputs and the second run on a full object table, shared by ``import_frames`` and
-    ``FrameSet.import_frames``: ``call`` takes the arguments of ``lc_import_frames`` from ``exptime`` on."""
+    ``FrameSet.import_frames``: ``call`` takes the arguments of ``lc_import_frames`` from ``exptime`` on, or with
+    ``deblend`` those of ``lc_import_frames_deblended``."""
     K, h, w = shape
     t = np.ascontiguousarray(np.broadcast_to(np.asarray(exptimes, np.float32).reshape(-1), (K,)), dtype=np.float32)
     if not (np.isfinite(t) & (t > 0)).all():
@@ -47,6 +51,8 @@ def _import(call, shape, exptimes, n_boxes, mask_sources_first, detection_thresh
     bcfg = _lib.BackgroundCfg(box, box, 3, 3, 0.0)
     ecfg = sep.extract_cfg(detection_threshold, min_area)
     mcfg = sep.extract_cfg(MASK_THRESH, MASK_MINAREA)
+    dcfg = sep.deblend_cfg(deblend)
+    catalogue = (C.byref(ecfg),) if dcfg is None else (C.byref(ecfg), C.byref(dcfg))
     ny, nx = sep.mesh_shape(h, w, box, box)
     out = dict(sub=np.empty(shape, np.float32) if with_sub else None, mesh_back=np.empty((K, ny, nx), np.float32),
                mesh_rms=np.empty((K, ny, nx), np.float32), globalback=np.empty(K, np.float32),
@@ -59,7 +65,7 @@ def _import(call, shape, exptimes, n_boxes, mask_sources_first, detection_thresh
     for attempt in range(2):
         table = np.zeros((K, cap), _lib.EXTRACT_OBJECT_DTYPE)
         ms = C.c_float()
-        call(ptr(t), C.byref(bcfg), C.byref(ecfg), int(bool(mask_sources_first)), C.byref(mcfg), cap,
+        call(ptr(t), C.byref(bcfg), *catalogue, int(bool(mask_sources_first)), C.byref(mcfg), cap,
              ptr(out['sub']), ptr(out['mesh_back']), ptr(out['mesh_rms']), ptr(out['globalback']), ptr(out['globalrms']),
              out['status'].ctypes.data_as(_i32p), table.ctypes.data_as(C.c_void_p), out['nobj'].ctypes.data_as(_i32p),
              out['segmap'].ctypes.data_as(_i32p) if segmentation_map else None, out['ex_status'].ctypes.data_as(_i32p),
@@ -72,8 +78,8 @@ def _import(call, shape, exptimes, n_boxes, mask_sources_first, detection_thresh
     return out
 
 
-def _characterize_stack(stack, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, ctx):
-    r = import_frames(stack, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, ctx=ctx)
+def _characterize_stack(stack, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, ctx, deblend=False):
+    r = import_frames(stack, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area, ctx=ctx, deblend=deblend)
     out = []
     for k in range(stack.shape[0]):
         if int(r['ex_status'][k]) == 2:
@@ -88,14 +94,16 @@ def _characterize_stack(stack, exptimes, n_boxes, mask_sources_first, detection_
     return out
 
 
-def characterize_frames(frames, exptimes, n_boxes=10, mask_sources_first=False, detection_threshold=3, min_area=10, ctx=None):
+def characterize_frames(frames, exptimes, n_boxes=10, mask_sources_first=False, detection_threshold=3, min_area=10, ctx=None,
+                        deblend=False):
     """What the reference computes of every frame it imports, for a (K, h, w) stack (one device call) or a list of frames
     of mixed shapes (one call per shape, in sorted order of the shapes).  ``exptimes``: one per frame, or one for all.
     Returns one dict per frame, in the order of ``frames``: image_sub, bkg (a ``sep.Background``), sources_table,
-    seeing_pixels (-1.0 without sources), ellipticity (the nanmedian of the table's; NaN without sources)."""
+    seeing_pixels (-1.0 without sources), ellipticity (the nanmedian of the table's; NaN without sources).  ``deblend``:
+    False for the catalogue without de-blending and cleaning, True for the reference's call (sep's defaults)."""
     if isinstance(frames, np.ndarray) and frames.ndim == 3:
         t = np.broadcast_to(np.asarray(exptimes, np.float32).reshape(-1), (len(frames),))
-        return _characterize_stack(frames, t, n_boxes, mask_sources_first, detection_threshold, min_area, ctx)
+        return _characterize_stack(frames, t, n_boxes, mask_sources_first, detection_threshold, min_area, ctx, deblend)
     frames = [np.asarray(f, dtype=np.float32) for f in frames]
     if any(f.ndim != 2 for f in frames):
         raise ValueError('characterize_frames takes 2-D frames')
@@ -104,7 +112,7 @@ def characterize_frames(frames, exptimes, n_boxes=10, mask_sources_first=False, 
     for shape in sorted({f.shape for f in frames}):
         idx = [i for i, f in enumerate(frames) if f.shape == shape]
         res = _characterize_stack(np.stack([frames[i] for i in idx]), t[idx], n_boxes, mask_sources_first,
-                                  detection_threshold, min_area, ctx)
+                                  detection_threshold, min_area, ctx, deblend)
         for i, r in zip(idx, res):
             out[i] = r
     return out

@@ -1,8 +1,10 @@
 """The reference's ``extract_stars`` (lightcurver/processes/star_extraction.py:8-55, called once per imported frame at
 frame_importation.py:130) over ``lightcurver_amd.sep.extract``: the catalogue of a background-subtracted frame as a table
-with the reference's columns.  The extraction runs WITHOUT de-blending and cleaning (DESIGN.md §5 "Source extraction of
-frames"), a declared deviation from the reference's call: a blended pair is one elongated object, which the elongation
-cut below mostly removes."""
+with the reference's columns.  By default the extraction runs WITHOUT de-blending and cleaning (DESIGN.md §5 "Source
+extraction of frames"): a blended pair is then one elongated object, which the elongation cut below mostly removes.
+That default differs from the reference's call, which leaves sep's ``deblend_cont=0.005`` and ``clean=True`` in place;
+``deblend=True`` is the reference's call (``sep.extract_deblended``, DESIGN.md §5 "De-blending and cleaning of frame
+objects"), not pinned against sep itself."""
 import numpy as np
 
 from .. import sep
@@ -37,8 +39,10 @@ def sources_table_from_objects(objects):
     return out[np.argsort(-out['flux'], kind='stable')]
 
 
-def extract_stars(image_background_subtracted, variance_map, detection_threshold=3, min_area=10, ctx=None):
+def extract_stars(image_background_subtracted, variance_map, detection_threshold=3, min_area=10, ctx=None, deblend=False):
     """The sources of a background-subtracted frame: ``variance_map`` a map or a scalar variance, the threshold in
-    sigma, the least number of pixels of a detection.  Returns ``sources_table_from_objects`` of the catalogue."""
-    objects = sep.extract(image_background_subtracted, detection_threshold, var=variance_map, minarea=min_area, ctx=ctx)
+    sigma, the least number of pixels of a detection.  ``deblend=True``: with sep's de-blending and cleaning, as the
+    reference calls it.  Returns ``sources_table_from_objects`` of the catalogue."""
+    extract = sep.extract_deblended if deblend else sep.extract
+    objects = extract(image_background_subtracted, detection_threshold, var=variance_map, minarea=min_area, ctx=ctx)
     return sources_table_from_objects(objects)

@@ -9,8 +9,9 @@ whose ``globalback`` and ``globalrms`` are arrays of K.  Only ``fw = fh`` of 1 o
 reference uses 3); anything else raises ``NotImplementedError``.
 
 ``extract`` is the SPEC "Source extraction of frames" of the same section: detection, 8-connected labelling and
-measurement of whole frames, that is ``sep.extract`` WITHOUT de-blending and WITHOUT cleaning.  There is no CPU
-fallback."""
+measurement of whole frames, that is ``sep.extract`` WITHOUT de-blending and WITHOUT cleaning.  ``extract_deblended``
+is ``sep.extract`` with both and with sep's own defaults (``lc_extract_frames_deblended``, the SPEC "De-blending and
+cleaning of frame objects"); it is not pinned against sep itself, which is absent here.  There is no CPU fallback."""
 import ctypes as C
 
 import numpy as np
@@ -153,6 +154,8 @@ OBJECT_FIELDS = ('x', 'y', 'a', 'b', 'theta', 'flux', 'npix', 'peak', 'cpeak', '
                  'ypeak', 'flag')
 OBJECT_DTYPE = np.dtype([(n, _lib.EXTRACT_OBJECT_DTYPE[n]) for n in OBJECT_FIELDS])
 FLAG_LARGE, FLAG_RANGE, FLAG_EDGE = 1, 2, 4
+FLAG_NODEBLEND = 8          # a parent whose box is over 64 pixels, or whose tree exceeds 32 leaves or 64 nodes: kept whole
+DEBLEND_DEFAULTS = dict(deblend_nthresh=32, deblend_cont=0.005, clean=True, clean_param=1.0)       # sep's
 _DEFAULT = object()
 
 
@@ -180,9 +183,31 @@ def extract_cfg(thresh, minarea, filter_kernel=_DEFAULT):
     return _lib.ExtractCfg(float(thresh), int(minarea), _filter_flag(filter_kernel))
 
 
+def deblend_cfg(deblend):
+    """``lc_deblend_cfg`` of ``deblend``: None or False -> None (no de-blending, no cleaning), True -> sep's defaults, a
+    dict -> those defaults with its entries (deblend_nthresh, deblend_cont, clean, clean_param)."""
+    if deblend is None or deblend is False:
+        return None
+    s = dict(DEBLEND_DEFAULTS)
+    if deblend is not True:
+        unknown = set(deblend) - set(s)
+        if unknown:
+            raise TypeError(f'deblend: unknown settings {sorted(unknown)}')
+        s.update(deblend)
+    if float(s['clean_param']) != 1.0:
+        raise NotImplementedError('extract: only clean_param = 1.0 is built')
+    if int(s['deblend_nthresh']) not in (4, 8, 16, 32):
+        raise NotImplementedError('extract: deblend_nthresh must be 4, 8, 16 or 32')
+    if not np.isfinite(s['deblend_cont']) or s['deblend_cont'] < 0:
+        raise ValueError(f"extract: deblend_cont = {s['deblend_cont']} must be finite and >= 0")
+    return _lib.DeblendCfg(int(s['deblend_nthresh']), float(s['deblend_cont']), int(bool(s['clean'])),
+                           float(s['clean_param']))
+
+
 def extract_frames(stack, var, thresh, minarea=5, filter_kernel=_DEFAULT, max_objects=8192, segmentation_map=False,
-                   mask=False, objects=True, ctx=None):
-    """One device call over a (K, h, w) stack.  ``var``: a (K, h, w) stack of variances, or one variance per frame
+                   mask=False, objects=True, ctx=None, deblend=None):
+    """One device call over a (K, h, w) stack.  ``deblend``: None for ``lc_extract_frames``; True (sep's defaults) or a
+    dict of deblend_nthresh, deblend_cont, clean, clean_param for ``lc_extract_frames_deblended``.  ``var``: a (K, h, w) stack of variances, or one variance per frame
     (a scalar or K of them).  Returns dict(objects: list of K record arrays of lc_extract_object (all its fields; None
     without ``objects``), nobj, status int32 (K,): 0, 1 = more objects than ``max_objects`` (the call is repeated once
     with the largest nobj, so 1 is not seen from here), 2 = the labelling's guard, segmap int32 (K, h, w) and mask uint8
@@ -192,6 +217,7 @@ def extract_frames(stack, var, thresh, minarea=5, filter_kernel=_DEFAULT, max_ob
         raise ValueError(f'expected a (K, h, w) stack of frames, got {d.shape}')
     K, h, w = d.shape
     cfg = extract_cfg(thresh, minarea, filter_kernel)
+    dcfg = deblend_cfg(deblend)
     if h < 1 or w < 1:
         raise ValueError(f'extract: frames of {h} x {w} pixels')
     if not extract_supported(h, w):
@@ -216,12 +242,16 @@ def extract_frames(stack, var, thresh, minarea=5, filter_kernel=_DEFAULT, max_ob
     for attempt in range(2):
         table = np.zeros((K, cap), _lib.EXTRACT_OBJECT_DTYPE) if objects else None
         ms = C.c_float()
-        ctx.check(_lib.lib().lc_extract_frames(
-            ctx.h, K, h, w, ptr(d), ptr(vplane), ptr(vscalar), C.byref(cfg), cap,
-            table.ctypes.data_as(C.c_void_p) if objects else None, out['nobj'].ctypes.data_as(_i32p),
-            out['segmap'].ctypes.data_as(_i32p) if segmentation_map else None,
-            out['mask'].ctypes.data_as(_u8p) if mask else None, out['status'].ctypes.data_as(_i32p), C.byref(ms)),
-            'lc_extract_frames')
+        outputs = (cap, table.ctypes.data_as(C.c_void_p) if objects else None, out['nobj'].ctypes.data_as(_i32p),
+                   out['segmap'].ctypes.data_as(_i32p) if segmentation_map else None,
+                   out['mask'].ctypes.data_as(_u8p) if mask else None, out['status'].ctypes.data_as(_i32p), C.byref(ms))
+        if dcfg is None:
+            ctx.check(_lib.lib().lc_extract_frames(ctx.h, K, h, w, ptr(d), ptr(vplane), ptr(vscalar), C.byref(cfg),
+                                                   *outputs), 'lc_extract_frames')
+        else:
+            ctx.check(_lib.lib().lc_extract_frames_deblended(ctx.h, K, h, w, ptr(d), ptr(vplane), ptr(vscalar),
+                                                             C.byref(cfg), C.byref(dcfg), *outputs),
+                      'lc_extract_frames_deblended')
         out['kernel_ms'] += ms.value
         if not objects or not (out['status'] == 1).any():
             break
@@ -245,6 +275,21 @@ def extract(data, thresh, err=None, var=None, mask=None, minarea=5, filter_kerne
         raise NotImplementedError('extract: de-blending is not built; pass deblend_cont=1.0 (sep\'s default is 0.005)')
     if clean:
         raise NotImplementedError('extract: cleaning is not built; pass clean=False (sep\'s default is True)')
+    return _extract_one(data, thresh, err, var, mask, minarea, filter_kernel, None, segmentation_map, max_objects, ctx)
+
+
+def extract_deblended(data, thresh, err=None, var=None, mask=None, minarea=5, filter_kernel=_DEFAULT, deblend_nthresh=32,
+                      deblend_cont=0.005, clean=True, clean_param=1.0, segmentation_map=False, max_objects=65536, ctx=None):
+    """``sep.extract`` of one frame with sep's own defaults: de-blending (``deblend_nthresh`` 4, 8, 16 or 32,
+    ``deblend_cont``; >= 1 switches it off) and cleaning (``clean``; only ``clean_param=1.0`` is built).  The other
+    arguments and the structured array it returns are those of ``extract``.  A parent whose box is over 64 pixels on a
+    side, or whose tree has more than 32 leaves or 64 nodes, stays whole and carries ``FLAG_NODEBLEND``."""
+    deblend = dict(deblend_nthresh=deblend_nthresh, deblend_cont=deblend_cont, clean=clean, clean_param=clean_param)
+    deblend_cfg(deblend)
+    return _extract_one(data, thresh, err, var, mask, minarea, filter_kernel, deblend, segmentation_map, max_objects, ctx)
+
+
+def _extract_one(data, thresh, err, var, mask, minarea, filter_kernel, deblend, segmentation_map, max_objects, ctx):
     _filter_flag(filter_kernel)
     d = f32(data)
     if d.ndim != 2:
@@ -267,7 +312,7 @@ def extract(data, thresh, err=None, var=None, mask=None, minarea=5, filter_kerne
             raise ValueError('mask must have the shape of the data')
         v = np.where(m, np.float32(np.nan), np.broadcast_to(v, d.shape)).astype(np.float32)
     r = extract_frames(d[None], v[None] if v.ndim == 2 else v, thresh, minarea, filter_kernel, max_objects,
-                       segmentation_map=segmentation_map, ctx=ctx)
+                       segmentation_map=segmentation_map, ctx=ctx, deblend=deblend)
     if int(r['status'][0]) == 2:
         raise _lib.LcError('extract: the iteration guard of the labelling was reached')
     objects = objects_view(r['objects'][0])

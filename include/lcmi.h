@@ -355,6 +355,35 @@ int lc_frames_cut_stamps(lc_frames *f, int S, int n, const int32_t *frame /*[S]*
                          float *data_out /*[S][n][n]*/, float *noisemap_out /*nullable*/, uint8_t *mask_out /*nullable*/,
                          int32_t *n_inside /*[S] nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- registration of source lists by star triangles (astroalign.find_transform), batched ----------------------------------
+ * The reference gives a frame its WCS from another frame's, or from Gaia positions, with one astroalign.find_transform per
+ * frame (lightcurver/processes/alternate_plate_solving_adapt_existing_wcs.py:24, alternate_plate_solving_with_gaia.py:66).
+ * lc_register_sources solves K such problems in one call, one workgroup each (DESIGN.md section 5 "Frame registration" is
+ * the SPEC; csrc/register.hip).  Problem k: the first nsrc[k] rows of src[k] against the first ntgt[k] rows of tgt[k],
+ * (x, y) float64, brightest first, already cut to the control points.  Outputs per problem:
+ *   transform  a, -b, tx, b, a, ty: target = [[a, -b], [b, a]] source + (tx, ty); NaN unless status is 0
+ *   pairs      the matched (source row, target row), by source row; -1 past npairs[k]
+ *   diag       source triangles, target triangles, matching triangle pairs, the winning hypothesis (-1: none), the inlier
+ *              matches of the final fit
+ *   status     0 solved; 1 no consensus (astroalign's MaxIterError), or a degenerate fit; 2 more than max_matches
+ *              matching triangle pairs; 3 fewer than three points on a side (astroalign's ValueError)
+ * A problem's status never affects another problem of the call, and its outputs do not depend on K or on its neighbours.
+ * kernel_ms spans both kernels and the one wait between them that sizes the table of matches.
+ * Checked on the host before anything is launched.  LC_ERR_INVALID: K < 1, a count outside [0, P], a coordinate inside a
+ * count that is not finite, a missing pointer, max_matches < 1, a tolerance or fraction that is not finite or not > 0.
+ * LC_ERR_UNSUPPORTED: P outside 3 .. 128 (lc_register_supported, no device needed). */
+typedef struct {
+  int32_t max_matches;         /* 65536 */
+  double pixel_tol;            /* 2.0: astroalign's PIXEL_TOL */
+  double invariant_radius;     /* 0.1: the radius of astroalign's query_ball_tree */
+  double min_matches_fraction; /* 0.8: astroalign's MIN_MATCHES_FRACTION */
+} lc_register_cfg;
+int lc_register_supported(int max_points);
+int lc_register_sources(lc_ctx *ctx, int K, int P, const double *src /*[K][P][2]*/, const int32_t *nsrc /*[K]*/,
+                        const double *tgt /*[K][P][2]*/, const int32_t *ntgt /*[K]*/, const lc_register_cfg *cfg,
+                        double *transform /*[K][6]*/, int32_t *pairs /*[K][P][2] nullable*/, int32_t *npairs /*[K]*/,
+                        int32_t *diag /*[K][5] nullable*/, int32_t *status /*[K]*/, float *kernel_ms /*nullable*/);
+
 /* ---- optimiser settings shared by both fits ----------------------------------------------- */
 /* optax.adabelief as driven by STARRED's Optimizer(method='adabelief'):
  * lightcurver/processes/star_photometry.py:113-122, roi_modelling.py:326-334. */

@@ -73,6 +73,11 @@ class DeblendCfg(C.Structure):
                 ('clean_param', C.c_float)]
 
 
+class RegisterCfg(C.Structure):
+    _fields_ = [('max_matches', C.c_int32), ('pixel_tol', C.c_double), ('invariant_radius', C.c_double),
+                ('min_matches_fraction', C.c_double)]
+
+
 class ExtractObject(C.Structure):
     _fields_ = [('first', C.c_int32), ('npix', C.c_int32), ('xmin', C.c_int32), ('xmax', C.c_int32), ('ymin', C.c_int32),
                 ('ymax', C.c_int32), ('xpeak', C.c_int32), ('ypeak', C.c_int32), ('flag', C.c_int32), ('pad', C.c_int32),
@@ -139,6 +144,9 @@ SIGNATURES = {
     'lc_cutout_supported': (C.c_int, [C.c_int, C.c_int]),
     'lc_frames_cut_stamps': (C.c_int, [vp, C.c_int, C.c_int, ip, ip, ip, fp, fp, C.c_int, C.c_int, C.POINTER(CosmicsCfg),
                                        C.POINTER(CcdmaskCfg), fp, fp, C.POINTER(C.c_uint8), ip, C.POINTER(C.c_float)]),
+    'lc_register_supported': (C.c_int, [C.c_int]),
+    'lc_register_sources': (C.c_int, [vp, C.c_int, C.c_int, dp, ip, dp, ip, C.POINTER(RegisterCfg), dp, ip, ip, ip, ip,
+                                      C.POINTER(C.c_float)]),
     'lc_ctx_stream': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     'lc_ctx_synchronize': (C.c_int, [vp]),
     'lc_timer_start': (C.c_int, [vp]),

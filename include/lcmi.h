@@ -462,6 +462,11 @@ int lc_psf_batch_get_results(lc_psf_batch *b, float *narrow_psf, float *full_psf
  * a, x0, y0).  One iteration = forward (resample B for every star) -> step of `stars` with export_grad -> backward
  * (adjoint resampling summed over the stars) -> step of `frames` with use_ext_grad; everything asynchronous. */
 int lc_psf_batch_set_moffat_q(lc_psf_batch *b, const float *q /* [F][4] = q11, q12, q22, beta */);
+/* Refused (LC_ERR_INVALID, nothing copied, the batch keeps the distortion it had), checked on the host for every (frame,
+ * star): a coefficient that is not finite or outside +-0.25; a coordinate that is not finite; an entry of the star's matrix
+ * A further than 0.5 from the identity (the range the adjoint resampling gathers without loss, csrc/psf_distort.h: with
+ * |x|, |y| <= 0.5 the coefficient bound keeps the entries inside it, pixel coordinates passed by mistake do not);
+ * det A <= 1e-3 (coefficients inside +-0.25 can make A singular).  The message names the frame and the star. */
 int lc_psf_batch_set_distortion(lc_psf_batch *frames, int S_stars, const float *coeffs /* [F][9] */,
                                 const float *xy /* [F][S_stars][2] rescaled frame coordinates */);
 int lc_psf_distortion_forward(lc_psf_batch *frames, lc_psf_batch *stars);
@@ -482,7 +487,9 @@ int lc_batched_lbfgs(int nb, int D, double *x, const double *lo, const double *h
  * (narrow_psf, kwargs_distortion read back from the regions file, rescaled star position).
  *   narrow_psf [N][N]; coeffs [9] = dilation_x (c0, c1, c2), dilation_y (c0, c1, c2), shear (c0, c1, c2), each evaluated
  *   as c0 + c1 x + c2 y; xy [K][2] rescaled frame coordinates of the K positions; out [K][N][N], unit sum each.
- * Host buffers, copied at call time; synchronous. */
+ * Host buffers, copied at call time; synchronous.
+ * Refused (LC_ERR_INVALID) before anything is copied or launched, `out` untouched: N <= 0, K <= 0, a coefficient or a
+ * position that is not finite, det A <= 1e-3 at any position (singular or inverting matrix; the message names it). */
 int lc_apply_distortion(lc_ctx *ctx, int N, int K, const float *narrow_psf, const float *coeffs,
                         const float *xy, float *out);
 

@@ -6,6 +6,8 @@
 //   A = [[1 + dilation_x, shear], [shear, 1 + dilation_y]];
 //   out[u][v] = bilinear_0(psf, c + A^-1 ((v, u) - c)),  c = (N - 1) // 2 (the zero-lag index: the PSF centre stays
 //   put), bilinear_0 = order-1 interpolation with zeros outside the grid; the result is renormalised to unit sum.
+#include <cstdio>
+
 #include "device_call.h"
 #include "lc_common.h"
 
@@ -13,7 +15,7 @@ using namespace lc;
 
 namespace {
 
-__device__ __forceinline__ void distortion_matrix(const float *coef, float x, float y, float &a00, float &a01, float &a11) {
+__host__ __device__ __forceinline__ void distortion_matrix(const float *coef, float x, float y, float &a00, float &a01, float &a11) {
   a00 = 1.f + coef[0] + coef[1] * x + coef[2] * y;
   a11 = 1.f + coef[3] + coef[4] * x + coef[5] * y;
   a01 = coef[6] + coef[7] * x + coef[8] * y;
@@ -64,6 +66,23 @@ extern "C" int lc_apply_distortion(lc_ctx *ctx, int N, int K, const float *narro
   LC_ENTER(ctx);
   for (int i = 0; i < 9; ++i)
     if (!std::isfinite(coeffs[i])) LC_FAIL(ctx, LC_ERR_INVALID, "lc_apply_distortion: non-finite coefficient");
+  // refused before anything is allocated, copied or launched (`out` stays untouched): a position that is not finite, and a
+  // singular or inverting matrix, which makes a meaningless PSF
+  for (int k = 0; k < K; ++k) {
+    const float x = xy[2 * k], y = xy[2 * k + 1];
+    char msg[200];
+    if (!std::isfinite(x) || !std::isfinite(y)) {
+      std::snprintf(msg, sizeof(msg), "lc_apply_distortion: position %d is not finite", k);
+      LC_FAIL(ctx, LC_ERR_INVALID, msg);
+    }
+    float a00, a01, a11;
+    distortion_matrix(coeffs, x, y, a00, a01, a11);
+    if (!(a00 * a11 - a01 * a01 > 1e-3f)) {
+      std::snprintf(msg, sizeof(msg), "lc_apply_distortion: distortion matrix is singular or inverting at position %d (%g, %g)", k,
+                    (double)x, (double)y);
+      LC_FAIL(ctx, LC_ERR_INVALID, msg);
+    }
+  }
   const size_t NN = (size_t)N * N;
   float *dpsf = nullptr, *dcoef = nullptr, *dxy = nullptr, *dout = nullptr;
   DevPool pool;
@@ -79,12 +98,5 @@ extern "C" int lc_apply_distortion(lc_ctx *ctx, int N, int K, const float *narro
   LC_HIP(ctx, hipGetLastError());
   LC_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)K * NN * sizeof(float), hipMemcpyDeviceToHost, q));
   LC_HIP(ctx, hipStreamSynchronize(q));
-  // a singular or inverting matrix makes a meaningless PSF: report it instead of returning zeros
-  for (int k = 0; k < K; ++k) {
-    const float x = xy[2 * k], y = xy[2 * k + 1];
-    const float a00 = 1.f + coeffs[0] + coeffs[1] * x + coeffs[2] * y, a11 = 1.f + coeffs[3] + coeffs[4] * x + coeffs[5] * y,
-                a01 = coeffs[6] + coeffs[7] * x + coeffs[8] * y;
-    if (!(a00 * a11 - a01 * a01 > 1e-3f)) LC_FAIL(ctx, LC_ERR_INVALID, "lc_apply_distortion: distortion matrix is singular or inverting");
-  }
   return LC_OK;
 }

@@ -1,5 +1,6 @@
 // PSF-fit batch object behind the C ABI (include/lcmi.h, "PSF fit" section).
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 
@@ -509,6 +510,31 @@ int lc_psf_batch_set_distortion(lc_psf_batch *b, int S_stars, const float *coeff
   for (size_t i = 0; i < (size_t)b->F * 9; ++i)
     if (!std::isfinite(coeffs[i]) || std::fabs(coeffs[i]) > 0.25f)
       LC_FAIL(b->ctx, LC_ERR_INVALID, "lc_psf_batch_set_distortion: coefficients must be finite and within +-0.25");
+  // what the resampling kernels hold for (csrc/psf_distort.h), per star and before anything is copied: the coefficient bound
+  // alone allows a singular matrix, and coordinates that are not the rescaled ones ([-0.5, 0.5]) allow any matrix
+  for (int f = 0; f < b->F; ++f)
+    for (int s = 0; s < S_stars; ++s) {
+      const float x = xy[((size_t)f * S_stars + s) * 2], y = xy[((size_t)f * S_stars + s) * 2 + 1];
+      const char *why = nullptr;
+      float a00 = 1.f, a01 = 0.f, a11 = 1.f;
+      if (!std::isfinite(x) || !std::isfinite(y)) {
+        why = "its coordinates are not finite";
+      } else {
+        distort_matrix(coeffs + (size_t)f * 9, x, y, a00, a01, a11);
+        if (!(std::fabs(a00 - 1.f) <= 0.5f && std::fabs(a11 - 1.f) <= 0.5f && std::fabs(a01) <= 0.5f))
+          why = "an entry of its matrix is further than 0.5 from the identity";
+        else if (!(a00 * a11 - a01 * a01 > 1e-3f))
+          why = "its matrix is singular (det <= 1e-3)";
+      }
+      if (why) {
+        char msg[320];
+        std::snprintf(msg, sizeof(msg),
+                      "lc_psf_batch_set_distortion: frame %d, star %d at (%g, %g): %s (A = [[%g, %g], [%g, %g]]; coordinates are "
+                      "the rescaled frame coordinates in [-0.5, 0.5])", f, s, (double)x, (double)y, why, (double)a00, (double)a01,
+                      (double)a01, (double)a11);
+        LC_FAIL(b->ctx, LC_ERR_INVALID, msg);
+      }
+    }
   int rc;
   if (b->dist_S != S_stars) {
     b->dist_coef = b->dist_xy = nullptr;  // earlier buffers stay in the allocation list until the object goes

@@ -14,7 +14,7 @@
 
 namespace lc {
 
-__device__ __forceinline__ void distort_matrix(const float *coef, float x, float y, float &a00, float &a01, float &a11) {
+__host__ __device__ __forceinline__ void distort_matrix(const float *coef, float x, float y, float &a00, float &a01, float &a11) {
   a00 = 1.f + coef[0] + coef[1] * x + coef[2] * y;
   a11 = 1.f + coef[3] + coef[4] * x + coef[5] * y;
   a01 = coef[6] + coef[7] * x + coef[8] * y;
@@ -110,8 +110,9 @@ __global__ __launch_bounds__(256) void psf_warp_kernel(int N, int S, const float
 }
 
 // exact adjoint, as a gather in a fixed order: source pixel k collects every destination pixel whose 2 x 2 footprint
-// contains it.  The distortion is close to the identity (|entries - identity| <= 0.25, enforced by the host), so those
-// lie within +-2 of the forward image of k.
+// contains it.  The host (lc_psf_batch_set_distortion) refuses a star whose matrix has an entry further than 0.5 from the
+// identity or det <= 1e-3: within 0.5 those destination pixels lie within +-2 of the forward image of k and no weight is
+// lost (beyond it the clamp of the window to 5 x 5 drops weights: ~1e-11 at 0.75, up to 0.02 at 1.0).
 __global__ __launch_bounds__(256) void psf_warp_adjoint_kernel(int N, int S, const float *coef, const float *xy, const float *g,
                                                                float *gsrc) {
   // grid (frames, ceil(N^2 / 256)): one source pixel per thread (one block per frame left 60 % of the CUs idle and took

@@ -222,6 +222,14 @@ def _fit_with_distortion(images, data, weight, norms, stars, moffat, S_list, coo
         if cf.shape[0] != S_list[f]:
             raise ValueError('stamp_coordinates must hold one (x, y) per stamp of the frame')
         xy[f, :S_list[f]] = cf
+    # The resampling kernels hold for matrices whose entries stay within 0.5 of the identity (csrc/psf_distort.h), and the
+    # library refuses others.  The fit lets every coefficient reach DISTORTION_BOUND, so an entry reaches
+    # DISTORTION_BOUND * (1 + |x| + |y|): coordinates for which that passes 0.5 are refused here, before anything is fitted.
+    reach = DISTORTION_BOUND * (1.0 + np.abs(xy).sum(axis=-1))
+    if not np.all(np.isfinite(xy)) or reach.max() > 0.5:
+        f, s = np.unravel_index(np.argmax(np.where(np.isfinite(reach), reach, np.inf)), reach.shape)
+        raise ValueError(f'stamp_coordinates of frame {f}, stamp {s} are ({xy[f, s, 0]:g}, {xy[f, s, 1]:g}): the field '
+                         f'distortion takes the rescaled frame coordinates, in [-0.5, 0.5] (pixel coordinates by mistake?)')
     star_b = PsfBatch(data.reshape(F * S, 1, n, n), weight.reshape(F * S, 1, n, n), ss, ctx)
     frame_b = PsfBatch(np.zeros((F, 1, n, n)), np.zeros((F, 1, n, n)), ss, ctx)
     lib = _lib.lib()
@@ -309,7 +317,11 @@ def _fit_with_distortion(images, data, weight, norms, stars, moffat, S_list, coo
         finally:
             tmp.close()
         frame_b.set_regularization(W, lam_scales, lam_hf)
-        frame_b.set_distortion(S, theta[:, 4:13], xy)
+        try:
+            frame_b.set_distortion(S, theta[:, 4:13], xy)
+        except _lib.LcError as exc:   # (a matrix out of range or singular; the message names the frame and the star)
+            raise ValueError(f'the fitted field distortion cannot be resampled - are stamp_coordinates the rescaled frame '
+                             f'coordinates in [-0.5, 0.5]? {exc}') from exc
         star_b.set_regularization(None, 0.0, 0.0)
         cfg = dict(init_learning_rate=init_learning_rate, schedule_learning_rate=schedule_learning_rate)
         # per iteration: B resampled for every star -> step of the stars (chi2, its gradients, a, x0, y0) -> d chi2 / d B

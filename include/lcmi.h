@@ -601,6 +601,27 @@ int lc_joint_fisher_flux_sigma(lc_joint *j, float *sigma_a);
  * not above 1e-6 times its diagonal entry) has NaN cov and sigma, the call still succeeds.  Same scope as
  * lc_joint_fisher_flux_sigma (batched star photometry: every epoch with its own star), whose 1 / sqrt(F_ii) it matches. */
 int lc_joint_fisher_flux_cov(lc_joint *j, float *fisher, float *cov, float *sigma);
+/* Fisher information with the source positions free: theta = (a [E * M], c_x [M], c_y [M], optionally mean [E]), everything
+ * else (dx, dy, alpha, h) fixed at its current value - the result is conditional on the registration and the background.
+ * F = J^T diag(1 / sigma^2) J (Gauss-Newton, independent of the data) is an arrowhead: per-epoch local blocks F_local
+ * (a_e, then mean_e), one shared block F_shared (c_x, then c_y; summed over the epochs in epoch order) and the couplings
+ * F_cross.  The C outputs are the blocks of F^-1 (Schur complement in float64): marginal covariances.  LC_FISHER_PRIOR adds
+ * 1 / sigma_p^2 of the Gaussian prior last given to lc_joint_set_loss to the diagonal of F_shared; no other regulariser
+ * enters.  A parameter whose diagonal entry is zero (prior included) is left out: sigma = +inf, zero rows and columns of C.
+ * A Cholesky pivot of any local block or of the Schur complement that is not above 1e-6 times its diagonal entry makes every
+ * C and sigma output NaN (F stays as computed, the call returns LC_OK).  Without LC_FISHER_POSITIONS the call is the flux
+ * (+ mean) covariance and the shared outputs must be NULL; sigma_mean must be NULL without LC_FISHER_MEAN; LC_FISHER_PRIOR
+ * needs LC_FISHER_POSITIONS (LC_ERR_INVALID).  LC_ERR_UNSUPPORTED: a batched star-photometry object; LC_FISHER_PRIOR when
+ * the loss has no prior.  Every refusal happens before a launch, outputs untouched. */
+#define LC_FISHER_POSITIONS 1   /* c_x, c_y free (both or neither) */
+#define LC_FISHER_MEAN      2   /* mean_e free */
+#define LC_FISHER_PRIOR     4   /* add the loss's Gaussian prior on c_x, c_y to F_shared */
+typedef struct {                /* every pointer may be NULL; Lp = M + (flags & LC_FISHER_MEAN ? 1 : 0) */
+  float *F_local, *F_cross, *F_shared;   /* [E][Lp][Lp], [E][Lp][2M], [2M][2M] */
+  float *C_local, *C_cross, *C_shared;   /* same shapes: marginal covariances */
+  float *sigma_a, *sigma_mean, *sigma_c; /* [E*M], [E], [2M] */
+} lc_fisher_positions_out;
+int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_out *out);
 /* Multi-GPU epoch sharding: split one optimiser step around the caller's all-reduce of the shared block
  * [dL/dh (N*N) | dL/dc_x (M) | dL/dc_y (M) | sum_e (a - ref) (M) | sum_e (a - ref)^2 (M) | chi2 | n_epochs]
  * living in device memory.  The flux moments (flux-uniformity term, jnp.std over epochs in the reference:

@@ -18,10 +18,12 @@
 #include "joint_noise.h"
 #include "joint_lbfgs.h"
 #include "joint_fisher.h"
+#include "joint_fisher_positions.h"
 #include "noise_host.h"
 #include "starlet_norms.h"
 
 using namespace lc;
+static_assert(kFpMaxSources == kMaxSources && kFpPivot == kFisherPivot, "joint_fisher_positions.h restates these");
 
 constexpr int kMaxParts = 16;  // workgroups per epoch of the phased launches
 constexpr int kRegChainCUs = 64;  // CUs the cluster form of the epoch kernel leaves to the regulariser chain beside it (cluster_parts)
@@ -166,6 +168,12 @@ struct lc_joint {
   // F, C [E][M][M], sigma [E][M] one after the other
   float *tmpl = nullptr, *fcov = nullptr;
   int fcov_chunk = 0;
+  // lc_joint_fisher_positions (allocated on first use): the column slab [fpos_chunk][n*n][32] of one chunk of epochs, the
+  // float64 work space of the solve, the float outputs one after the other and the factorisation flags [E + 1]
+  float *fpos_slab = nullptr, *fpos_out = nullptr;
+  double *fpos_work = nullptr;
+  int *fpos_ok = nullptr;
+  int fpos_chunk = 0;
   DevPool pool;  // everything dmalloc handed out; hist, ghist and phist are grown and freed on their own
 };
 
@@ -2669,6 +2677,90 @@ int lc_joint_fisher_flux_cov(lc_joint *j, float *fisher, float *cov, float *sigm
   if (fisher) std::memcpy(fisher, host.data(), EMM * sizeof(float));
   if (cov) std::memcpy(cov, host.data() + EMM, EMM * sizeof(float));
   if (sigma) std::memcpy(sigma, host.data() + 2 * EMM, (size_t)E * M * sizeof(float));
+  return LC_OK;
+}
+
+int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_out *out) {
+  if (!j || !out || (flags & ~(LC_FISHER_POSITIONS | LC_FISHER_MEAN | LC_FISHER_PRIOR))) return LC_ERR_INVALID;
+  LC_ENTER(j->ctx);
+  const bool positions = flags & LC_FISHER_POSITIONS, mean = flags & LC_FISHER_MEAN, prior = flags & LC_FISHER_PRIOR;
+  if (!positions && (out->F_cross || out->F_shared || out->C_cross || out->C_shared || out->sigma_c))
+    LC_FAIL(j->ctx, LC_ERR_INVALID, "lc_joint_fisher_positions: shared outputs need LC_FISHER_POSITIONS");
+  if (!mean && out->sigma_mean) LC_FAIL(j->ctx, LC_ERR_INVALID, "lc_joint_fisher_positions: sigma_mean needs LC_FISHER_MEAN");
+  if (prior && !positions) LC_FAIL(j->ctx, LC_ERR_INVALID, "lc_joint_fisher_positions: LC_FISHER_PRIOR needs LC_FISHER_POSITIONS");
+  if (j->G > 0)
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_positions: not available on a batched star-photometry object (positions are per star)");
+  if (prior && j->n_prior == 0) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_positions: LC_FISHER_PRIOR, but the loss has no prior on c_x, c_y");
+  const int E = j->E, M = j->M, n = j->n, nn = n * n;
+  if (E == 0) return LC_OK;
+  const int Lp = M + (mean ? 1 : 0), Sh = positions ? 2 * M : 0;
+  const size_t lds = fisher_tmpl_lds(n, j->ss);
+  if (lds > 64 * 1024) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_positions: stamp size beyond the template kernel's LDS");
+  // outputs at their largest (mean and positions free), one after the other
+  const size_t LM = (size_t)M + 1, SM = 2 * (size_t)M;
+  const size_t cap = 2 * ((size_t)E * LM * LM + (size_t)E * LM * SM + SM * SM) + (size_t)E * M + E + SM;
+  constexpr size_t kPerEpoch = kFpCols * kFpCols + kFpLocal * kFpLocal + kFpLocal * kFpShared + kFpShared * kFpShared;
+  if (!j->fpos_slab) {  // epochs per chunk: a slab of about 64 MiB
+    const size_t per = (size_t)kFpCols * nn * sizeof(float);
+    j->fpos_chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)E, ((size_t)64 << 20) / per));
+    int rc = dmalloc(j, &j->fpos_slab, (size_t)j->fpos_chunk * nn * kFpCols);
+    if (!rc) rc = dmalloc(j, &j->fpos_work, (size_t)E * kPerEpoch + kFpShared * kFpShared);
+    if (!rc) rc = dmalloc(j, &j->fpos_out, cap);
+    if (!rc) rc = dmalloc(j, &j->fpos_ok, (size_t)E + 1);
+    if (rc) return rc;
+  }
+  hipStream_t q = j->ctx->stream;
+  FisherArrowArgs S{};
+  S.Fd = j->fpos_work;
+  S.Binv = j->fpos_work + (size_t)E * kFpCols * kFpCols;
+  S.B = S.Binv + (size_t)E * kFpLocal * kFpLocal;
+  S.G = S.B + (size_t)E * kFpLocal * kFpShared;
+  S.Ccc = S.G + (size_t)E * kFpShared * kFpShared;
+  S.ok = j->fpos_ok;
+  S.prior = prior ? j->prior : nullptr;
+  S.E = E;
+  S.M = M;
+  S.Lp = Lp;
+  S.Sh = Sh;
+  const size_t nFl = (size_t)E * Lp * Lp, nFx = (size_t)E * Lp * Sh, nFs = (size_t)Sh * Sh;
+  S.F_local = j->fpos_out;
+  S.F_cross = S.F_local + nFl;
+  S.F_shared = S.F_cross + nFx;
+  S.C_local = S.F_shared + nFs;
+  S.C_cross = S.C_local + nFl;
+  S.C_shared = S.C_cross + nFx;
+  S.sigma_a = S.C_shared + nFs;
+  S.sigma_mean = S.sigma_a + (size_t)E * M;
+  S.sigma_c = S.sigma_mean + E;
+  const size_t used = (size_t)(S.sigma_c + Sh - j->fpos_out);
+  const int bands = (n + kFpBand - 1) / kFpBand;
+  for (int e0 = 0; e0 < E; e0 += j->fpos_chunk) {
+    const int e1 = std::min(E, e0 + j->fpos_chunk);
+    FisherTmplArgs T{j->psf_dev, j->wgt, j->par[LC_P_A], j->par[LC_P_CX], j->par[LC_P_CY], j->par[LC_P_DX], j->par[LC_P_DY],
+                     j->par[LC_P_ALPHA], j->fpos_slab, e0, M, n, j->ss, j->N, positions ? 1 : 0, mean ? 1 : 0};
+    launch_fisher_tmpl(T, bands, std::max(M, 1), e1 - e0, lds, q);
+    LC_HIP(j->ctx, hipGetLastError());
+    FisherGramArgs Gm{j->fpos_slab, nn, j->fpos_work + (size_t)e0 * kFpCols * kFpCols};
+    launch_fisher_gram(Gm, e1 - e0, q);
+    LC_HIP(j->ctx, hipGetLastError());
+  }
+  launch_fisher_arrow(S, q);
+  LC_HIP(j->ctx, hipGetLastError());
+  std::vector<float> host(used);
+  int rc = d2h(j, host.data(), j->fpos_out, used * sizeof(float));
+  if (rc) return rc;
+  auto give = [&](float *dst, const float *src, size_t count) {
+    if (dst && count) std::memcpy(dst, host.data() + (src - j->fpos_out), count * sizeof(float));
+  };
+  give(out->F_local, S.F_local, nFl);
+  give(out->F_cross, S.F_cross, nFx);
+  give(out->F_shared, S.F_shared, nFs);
+  give(out->C_local, S.C_local, nFl);
+  give(out->C_cross, S.C_cross, nFx);
+  give(out->C_shared, S.C_shared, nFs);
+  give(out->sigma_a, S.sigma_a, (size_t)E * M);
+  give(out->sigma_mean, S.sigma_mean, mean ? (size_t)E : 0);
+  give(out->sigma_c, S.sigma_c, (size_t)Sh);
   return LC_OK;
 }
 

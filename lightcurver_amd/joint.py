@@ -83,6 +83,7 @@ class JointFit:
         w = None if W is None else self._weight_cube(W)
         self._keep = (keep, w)
         self._chk(self._l.lc_joint_set_loss(self.h, C.byref(cfg), ptr(w)), 'set_loss')
+        self._has_prior = prior is not None
 
     def _weight_cube(self, W):
         """W as set_loss hands it to the device: the first J scales, float32."""
@@ -216,6 +217,31 @@ class JointFit:
         self._chk(self._l.lc_joint_fisher_flux_cov(self.h, ptr(F), ptr(Cv), ptr(s)), 'fisher_flux_cov')
         return F, Cv, s
 
+    def fisher_positions(self, positions=True, mean=False, prior=None):
+        """Fisher information with the source positions free (lc_joint_fisher_positions): theta = (a, c_x, c_y[, mean]),
+        everything else (dx, dy, alpha, h) fixed at its current value - conditional on the registration and the background.
+        Gauss-Newton F = J^T diag(1 / sigma^2) J, an arrowhead; returns a dict of its blocks and of the blocks of F^-1
+        (Lp = M + 1 with ``mean``, else M):
+          F_local, C_local (E, Lp, Lp)   a_e then mean_e;      F_cross, C_cross (E, Lp, 2M);
+          F_shared, C_shared (2M, 2M)    c_x then c_y;         sigma_a (E * M,), sigma_mean (E,), sigma_c (2M,)
+        the sigmas marginal (sqrt of the diagonal of F^-1).  ``positions=False``: the flux (+ mean) covariance alone, the
+        shared arrays empty; ``mean=False``: sigma_mean empty.  ``prior``: add the Gaussian prior on c_x, c_y last given to
+        set_loss to F_shared - None: if one is set.  A parameter with a zero diagonal entry has sigma = inf and zero rows and
+        columns of C; a numerically singular local block or Schur complement makes every C and sigma NaN."""
+        if prior is None:
+            prior = bool(positions) and getattr(self, '_has_prior', False)
+        E, M = self.E, self.M
+        Lp, Sh = M + (1 if mean else 0), (2 * M if positions else 0)
+        shapes = {'F_local': (E, Lp, Lp), 'F_cross': (E, Lp, Sh), 'F_shared': (Sh, Sh), 'C_local': (E, Lp, Lp),
+                  'C_cross': (E, Lp, Sh), 'C_shared': (Sh, Sh), 'sigma_a': (E * M,), 'sigma_mean': (E if mean else 0,),
+                  'sigma_c': (Sh,)}
+        res = {k: np.zeros(shapes[k], np.float32) for k in _lib.FISHER_POSITIONS_FIELDS}
+        out = _lib.FisherPositionsOut(*[ptr(res[k]) if res[k].size else None for k in _lib.FISHER_POSITIONS_FIELDS])
+        flags = ((_lib.FISHER_POSITIONS if positions else 0) | (_lib.FISHER_MEAN if mean else 0)
+                 | (_lib.FISHER_PRIOR if prior else 0))
+        self._chk(self._l.lc_joint_fisher_positions(self.h, flags, C.byref(out)), 'fisher_positions')
+        return res
+
     # multi-GPU split step (epoch sharding)
     def step_local(self):
         self._chk(self._l.lc_joint_step_local(self.h), 'step_local')
@@ -330,6 +356,9 @@ class StarPhotometryBatch(JointFit):
         hist = np.empty((self.G, T + 1), np.float32)
         self._chk(self._l.lc_joint_get_group_loss_history(self.h, ptr(hist), T + 1), 'get_group_loss_history')
         return hist
+
+    def fisher_positions(self, positions=True, mean=False, prior=None):
+        raise NotImplementedError('fisher_positions: the positions of a batched star photometry are per star')
 
     def split(self, flat, name):
         """The concatenated block ``name`` as a list of per-star arrays."""

@@ -17,7 +17,7 @@ from ..starred.deconvolution.loss import Loss, Prior
 from ..starred.deconvolution.parameters import ParametersDeconv
 from ..starred.optim.optimization import Optimizer
 from ..starred.utils.noise_utils import propagate_noise
-from ..utilities.starred_utilities import get_flux_uncertainties
+from ..utilities.starred_utilities import _polished_fisher, get_flux_uncertainties, position_covariance_of
 
 DEFAULT_REGULARIZATION = {  # code fall-backs of the reference (roi_modelling.py:273,308-312)
     'regularization_scatter_fluxes_pre_optim': 10.0,
@@ -52,13 +52,19 @@ def initial_point_source_fluxes(data, xs, ys, radius):
 def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pixels, angles_to_north=None,
                       initial_a=None, aperture_radius=3.0, fix_point_source_astrometry=False,
                       starting_background=None, further_optimize_background=True, regularization=None,
-                      roi_deconv_translations_iters=300, roi_deconv_all_iters=2000, rescale=True):
+                      roi_deconv_translations_iters=300, roi_deconv_all_iters=2000, rescale=True,
+                      marginalize_positions=False):
     """data, noisemap (E, n, n); psf (E, N, N); xs_pixels, ys_pixels: point-source positions in pixels of
     the first epoch (0-based, as astropy's world_to_pixel returns them).
 
     Returns a dict: kwargs_final, kwargs_stage1, loss_history (stage 2), loss_history_stage1, scale, model,
-    and the pieces needed downstream (model object, kwargs_up / kwargs_down).
+    and the pieces needed downstream (model object, kwargs_up / kwargs_down).  ``marginalize_positions``: also
+    ``astrometry_uncertainties`` = {'c_x_sigma', 'c_y_sigma' (M, data pixels), 'covariance' (2M, 2M; c_x, then c_y)} and
+    ``fluxes_sigma`` (E * M, in the units of kwargs_final), from the Fisher information at the final point with the fluxes
+    and the positions free (the astrometric prior of the fit included; conditional on dx, dy, alpha and h).
     """
+    if marginalize_positions and isinstance(fix_point_source_astrometry, bool) and fix_point_source_astrometry:
+        raise ValueError('marginalize_positions: the positions are fixed (fix_point_source_astrometry=True)')
     reg = dict(DEFAULT_REGULARIZATION)
     reg.update(regularization or {})
     data = np.array(data, dtype=np.float64)
@@ -130,15 +136,21 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
     # position of the sources in the first epoch, back in pixels (roi_modelling.py:339-340)
     x_pix = np.array(k_final['kwargs_analytic']['c_x']) + np.array(k_final['kwargs_analytic']['dx'])[0] + offset
     y_pix = np.array(k_final['kwargs_analytic']['c_y']) + np.array(k_final['kwargs_analytic']['dy'])[0] + offset
-    return dict(kwargs_final=k_final, kwargs_stage1=k_stage1, loss_history=optim2.loss_history,
-                loss_history_stage1=optim1.loss_history, scale=scale, model=model, kwargs_up=k_up, kwargs_down=k_down,
-                data=data, noisemap=noisemap, x_pixels=x_pix, y_pixels=y_pix, W=W)
+    out = dict(kwargs_final=k_final, kwargs_stage1=k_stage1, loss_history=optim2.loss_history,
+               loss_history_stage1=optim1.loss_history, scale=scale, model=model, kwargs_up=k_up, kwargs_down=k_down,
+               data=data, noisemap=noisemap, x_pixels=x_pix, y_pixels=y_pix, W=W)
+    if marginalize_positions:
+        fisher = _polished_fisher(k_final, k_up, k_down, data, noisemap, model, 0, False, free_positions=True, prior=prior)
+        cov, sx, sy = position_covariance_of(fisher)
+        out['astrometry_uncertainties'] = {'c_x_sigma': sx, 'c_y_sigma': sy, 'covariance': cov}
+        out['fluxes_sigma'] = np.array(fisher.get_kwargs_sigma()['kwargs_analytic']['a'], dtype=np.float64)
+    return out
 
 
 def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pixels, initial_a, scale,
                               group=None, use_peer=False, regularization=None, roi_deconv_translations_iters=300,
                               roi_deconv_all_iters=2000, further_optimize_background=True, ctx=None,
-                              return_flux_covariance=False):
+                              return_flux_covariance=False, marginalize_positions=False):
     """The two-stage fit of ``model_roi_cutouts`` with the epochs spread over the ranks of a torch.distributed group (one
     process per GPU): every rank passes ITS epochs - data, noisemap (E_local, n, n), psf (E_local, N, N) - and the same
     ``initial_a`` (M fluxes) and ``scale`` (nanmax of the data of ALL epochs: ``global_scale``).  The reference has no
@@ -151,7 +163,10 @@ def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels
     ``use_peer``: by the one-shot peer-memory kernel).  Returns, on every rank, the parameters of ALL epochs (gathered), the
     loss histories and the Fisher 1-sigma of the fluxes at the final point.  ``return_flux_covariance``: also the (E, M, M)
     covariance blocks of the fluxes of all epochs (``fluxes_covariance``: every rank its epochs', gathered in the order of
-    ``fluxes_sigma``)."""
+    ``fluxes_sigma``).  ``marginalize_positions`` is not built here (NotImplementedError): the Schur complement of the
+    positions sums over the epochs of all ranks."""
+    if marginalize_positions:
+        raise NotImplementedError('marginalize_positions in the sharded ROI fit: the Schur sum crosses the ranks')
     import torch
     import torch.distributed as dist
     from ..distributed import PeerGroup, ShardedJointOptimizer, gather_epoch_blocks, host_group
@@ -232,13 +247,23 @@ def global_scale(data, group=None):
 
 
 def fluxes_from_model(model, kwargs, kwargs_up, kwargs_down, data, noisemap, n_sources, model_scale,
-                      normalization_errors):
+                      normalization_errors, marginalize_positions=False, prior=None):
     """Numeric part of get_fluxes_dataframe_from_model (roi_modelling.py:450-474): per-source light
     curves (a is epoch-major: curve i = a[i::M]), their uncertainties (Fisher 1-sigma compounded with the
-    frame normalisation error), residuals and the per-frame reduced chi2."""
+    frame normalisation error), residuals and the per-frame reduced chi2.  ``marginalize_positions``: the photon error is
+    the marginal one with the fluxes and the positions c_x, c_y free (``prior``: the fit's ``Prior`` on them), and the
+    result gains ``astrometry_uncertainties`` = {'c_x_sigma', 'c_y_sigma', 'covariance'} (data pixels)."""
     a = np.array(kwargs['kwargs_analytic']['a'])
-    sigma_a = np.array(get_flux_uncertainties(kwargs=kwargs, kwargs_up=kwargs_up, kwargs_down=kwargs_down,
-                                              data=data, noisemap=noisemap, model=model))
+    astrometry = None
+    if marginalize_positions:
+        fisher = _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, 10, False, free_positions=True,
+                                  prior=prior)
+        sigma_a = np.array(fisher.get_kwargs_sigma()['kwargs_analytic']['a'], dtype=np.float64)
+        cov, sx, sy = position_covariance_of(fisher)
+        astrometry = {'c_x_sigma': sx, 'c_y_sigma': sy, 'covariance': cov}
+    else:
+        sigma_a = np.array(get_flux_uncertainties(kwargs=kwargs, kwargs_up=kwargs_up, kwargs_down=kwargs_down,
+                                                  data=data, noisemap=noisemap, model=model))
     norm_err = np.asarray(normalization_errors, dtype=np.float64)
     curves, d_curves = [], []
     for i in range(n_sources):
@@ -248,8 +273,11 @@ def fluxes_from_model(model, kwargs, kwargs_up, kwargs_down, data, noisemap, n_s
         d_curves.append(np.sqrt(photon ** 2 + (norm_err * curve) ** 2))
     residuals = data - model.model(kwargs)
     chi2_per_frame = np.nansum(residuals ** 2 / noisemap ** 2, axis=(1, 2)) / model.image_size ** 2
-    return dict(fluxes=np.array(curves), d_fluxes=np.array(d_curves), residuals=residuals,
-                reduced_chi2=np.array(chi2_per_frame))
+    out = dict(fluxes=np.array(curves), d_fluxes=np.array(d_curves), residuals=residuals,
+               reduced_chi2=np.array(chi2_per_frame))
+    if astrometry is not None:
+        out['astrometry_uncertainties'] = astrometry
+    return out
 
 
 # ---- diagnostics of roi_modelling.py:34-125 ---------------------------------------------

@@ -3,7 +3,11 @@ lightcurver/utilities/starred_utilities.py:10-39 obtains them from STARRED: ever
 fluxes is frozen at its fitted value, the fluxes are polished by a few L-BFGS-B iterations and the
 1-sigma is read off the Hessian diagonal of the chi2.  ``get_flux_covariance`` does the same and returns the
 covariance of the fluxes of every epoch (the inverse of the full Fisher information, block diagonal over the
-epochs), which ``flux_combination_sigma`` turns into the error of a sum of fluxes (blended images)."""
+epochs), which ``flux_combination_sigma`` turns into the error of a sum of fluxes (blended images).  With
+``free_positions`` (and ``free_mean``) the source positions c_x, c_y (the epochs' constants) are free in the information as
+well - ``FisherCovariance`` with those blocks free, conditional on dx, dy, alpha and h - and the covariances are marginal
+over them; ``get_position_covariance`` returns that of the positions.  The L-BFGS-B polish stays on the fluxes."""
+import warnings
 from copy import deepcopy
 
 import numpy as np
@@ -14,17 +18,31 @@ from ..starred.optim.inference_base import FisherCovariance
 from ..starred.optim.optimization import Optimizer
 
 
-def _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations, diagonal_only):
+def _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations, diagonal_only,
+                     free_positions=False, free_mean=False, prior=None):
     frozen = deepcopy(kwargs)
     frozen['kwargs_analytic'].pop('a')
     pars = ParametersDeconv(kwargs_init=kwargs, kwargs_fixed=frozen, kwargs_up=kwargs_up, kwargs_down=kwargs_down)
-    import warnings
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')  # "lambda is not normalized": h is frozen here, the term is a constant
         loss = Loss(data, model, pars, np.asarray(noisemap) ** 2, regularization_terms='l1_starlet')
     optim = Optimizer(loss, pars, method='l-bfgs-b')
     if refine_iterations > 0:
         optim.minimize(maxiter=int(refine_iterations))
+    if free_positions or free_mean:  # the information at the polished fluxes, with the further blocks free
+        best = deepcopy(pars.best_fit_values(as_kwargs=True)) if refine_iterations > 0 else deepcopy(kwargs)
+        frozen = deepcopy(best)
+        frozen['kwargs_analytic'].pop('a')
+        if free_positions:
+            frozen['kwargs_analytic'].pop('c_x')
+            frozen['kwargs_analytic'].pop('c_y')
+        if free_mean:
+            frozen['kwargs_background'].pop('mean')
+        pars = ParametersDeconv(kwargs_init=best, kwargs_fixed=frozen, kwargs_up=kwargs_up, kwargs_down=kwargs_down)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            loss = Loss(data, model, pars, np.asarray(noisemap) ** 2, regularization_terms='l1_starlet', prior=prior)
+        optim = Optimizer(loss, pars, method='l-bfgs-b')
     fisher = FisherCovariance(pars, optim, diagonal_only=diagonal_only)
     fisher.compute_fisher_information()
     return fisher
@@ -36,12 +54,33 @@ def get_flux_uncertainties(kwargs, kwargs_up, kwargs_down, data, noisemap, model
     return np.array(fisher.get_kwargs_sigma()['kwargs_analytic']['a'])
 
 
-def get_flux_covariance(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations=10):
+def get_flux_covariance(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations=10,
+                        free_positions=False, free_mean=False, prior=None):
     """(E, M, M): the covariance of the M fluxes of every epoch, after the same L-BFGS-B polish of the fluxes as
     ``get_flux_uncertainties``.  Its diagonal is the square of the marginal 1-sigma (the flux's error with the other
-    fluxes of its epoch free), which is at least that of ``get_flux_uncertainties`` (the others held fixed)."""
-    fisher = _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations, False)
+    fluxes of its epoch free), which is at least that of ``get_flux_uncertainties`` (the others held fixed).
+    ``free_positions`` / ``free_mean``: marginal over c_x, c_y / the epochs' constants as well (``prior``: the ``Prior`` on
+    c_x, c_y of the fit, which then enters the information); conditional on dx, dy, alpha and h."""
+    fisher = _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations, False,
+                              free_positions, free_mean, prior)
     return np.array(fisher.flux_covariance_blocks, dtype=np.float64)
+
+
+def position_covariance_of(fisher):
+    """(cov (2M, 2M), sigma_c_x (M), sigma_c_y (M)) of a ``FisherCovariance`` with the positions free."""
+    cov = np.array(fisher.position_covariance, dtype=np.float64)
+    sig = np.sqrt(np.diag(cov))
+    M = sig.size // 2
+    return cov, sig[:M], sig[M:]
+
+
+def get_position_covariance(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations=10, free_mean=False,
+                            prior=None):
+    """(cov (2M, 2M), sigma_c_x (M), sigma_c_y (M)): the marginal covariance of the source positions (c_x, then c_y; data
+    pixels) with the fluxes (and with ``free_mean`` the epochs' constants) free, dx, dy, alpha and h fixed."""
+    fisher = _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, refine_iterations, False, True,
+                              free_mean, prior)
+    return position_covariance_of(fisher)
 
 
 def flux_combination_sigma(cov, weights):

@@ -1,7 +1,9 @@
 """Ad-hoc timing of the flux errors: the diagonal Fisher call (fisher_flux_sigma, M epoch launches) against the full Fisher
 information (fisher_flux_covariance: the same M launches writing the template slab, the Gram-and-solve kernel, three copies
 back).  python tools/fisher_speed.py [reps] - at the C4 size (200 epochs of 64 x 64, M = 4) and one C5 shard (125 epochs of
-128 x 128, M = 8), background non-zero (the FFT epoch kernels) and zero (the point-source kernel where the size has one)."""
+128 x 128, M = 8), background non-zero (the FFT epoch kernels) and zero (the point-source kernel where the size has one).
+Then the information with the positions free (fisher_positions: template kernel, Gram kernel on the matrix cores, the float64
+arrowhead solve, one copy back) beside the flux-only covariance, at 200 x 64 x 64 and 125 x 128 x 128 with M = 4."""
 import os
 import sys
 import time
@@ -37,3 +39,26 @@ for name, E, n, M in (('C4', 200, 64, 4), ('C5-shard', 125, 128, 8)):
         j.close()
         print(f'{name} E={E} n={n} M={M} background={"on " if bg else "off"}: diagonal {res["diagonal"]:.3f} ms, '
               f'covariance {res["covariance"]:.3f} ms, ratio {res["covariance"] / res["diagonal"]:.2f}', flush=True)
+
+for name, E, n, M in (('C4', 200, 64, 4), ('C5-shard', 125, 128, 4)):
+    ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=11, with_background=True)
+    p = {k: np.asarray(v, np.float64) for k, v in ds['truth'].items()}
+    j = JointFit(ds['data'], ds['noisemap'].astype(np.float64) ** 2, ds['psf'], 2, M, ctx)
+    j.set_params(**p)
+    j.set_free(['a'])
+    calls = (('flux covariance', j.fisher_flux_covariance), ('positions free', j.fisher_positions),
+             ('positions + mean free', lambda: j.fisher_positions(mean=True)),
+             ('fluxes only, new path', lambda: j.fisher_positions(positions=False)))
+    for _, fn in calls:
+        fn()                         # (first calls: the slabs are allocated)
+    ctx.synchronize()
+    res = {}
+    for label, fn in calls:
+        t = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            t.append(time.perf_counter() - t0)
+        res[label] = float(np.median(t)) * 1e3
+    j.close()
+    print(f'{name} E={E} n={n} M={M}: ' + ', '.join(f'{k} {v:.3f} ms' for k, v in res.items()), flush=True)

@@ -26,6 +26,10 @@
 #ifndef LC_STARLET_LIVE_ADDR
 #define LC_STARLET_LIVE_ADDR 1  // two workgroups, pixel state in registers: the starlet keeps its transpose addresses live
 #endif
+// DESIGN.md, "PSF fit: the serial head and tail of role 0's iteration" (make alt ALTFLAGS=-DLC_SERIAL_TRIM=0 for the order before it)
+#ifndef LC_SERIAL_TRIM
+#define LC_SERIAL_TRIM 1  // C2, two workgroups: role 0 publishes straight behind P5 and writes T of the next iteration behind its pixel step
+#endif
 namespace lc {
 constexpr int kXFlagStride = 16;   // flag words per (frame, role): word 0 is the flag, the rest keeps (frame, role) pairs on lines of their own
 
@@ -216,7 +220,8 @@ __device__ inline void tap_entry(float delta, int k, float &tap, float &dtap, in
 // Block b serves frame (b / 16) * 8 + b % 8 in role (b / 8) % 2: partners are 8 blocks apart, which the
 // dispatcher is observed to place on one XCD (speed only).  The host launches this form only when the whole grid
 // is resident at once (one workgroup per CU), so the partner a workgroup waits for is always running.
-// Hand-off protocol of iteration t, the same in both roles: store the own half into slab t & 1 (role 1: and its l1 value), every
+// Hand-off protocol of iteration t, the same in both roles (but see the last item for role 0 of C2):
+// store the own half into slab t & 1 (role 1: and its l1 value), every
 // wave drains its stores, workgroup barrier, ONE lane stores t + 1 into the own flag and polls the partner's flag for t + 1
 // (bounded), barrier, every thread loads the partner's half with L1-bypassing loads, step, closing barrier.
 // * Flag first.  Each role publishes before it waits, so there is no wait cycle, and neither role's publishing depends on the
@@ -230,6 +235,16 @@ __device__ inline void tap_entry(float delta, int k, float &tap, float &dtap, in
 // * Pixel state in registers (N <= 64): between its stores and its flag role 0 runs only the step of the stars (first wave,
 //   beside the drain); the tap tables of the next iteration, which need that step, are made behind the drain's barrier while
 //   the one lane stores and polls.  N = 128: stars' step, barrier and tables all beside the drain, as before.
+// * C2 (N = 64, 8 pixels per thread; TRIM in the kernel): role 0's hand-off of iteration t reads
+//     last star of P5, ext_grad; every wave stores its half of slab t & 1; ONE workgroup barrier (REDX and SGR visible);
+//     first wave: x0 sums, wave-level LDS sync, stars' step - beside the drain; every wave drains;
+//     barrier; flag, poll and tap tables; barrier; loads; pixel step; T of iteration t + 1 and the loss; closing barrier,
+//   which is also the barrier that opens the first group of stars of iteration t + 1.  Role 0 runs no l1 sum and not the barrier
+//   behind it (its l1 is identically zero); role 1 keeps both, its l1 value rides with its slab.  The two-slab argument
+//   does not depend on where inside iteration t a role stores: role 0's stores of iteration t come behind its poll of
+//   iteration t - 1, which saw the partner's flag t, and the partner raises flag t only at iteration t - 1, behind its loads
+//   of iteration t - 2 (they end in s_waitcnt vmcnt(0)) - the last reads of slab t & 1 before these stores.  So the
+//   stores may stand anywhere in iteration t, and straight behind P5 they need nothing but the thread's own gB.
 template <class C, bool SPLIT = false>
 __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
   constexpr int N = C::N, SS = C::SS, PX = C::PX, SG = C::SG, n = C::n, NT = C::NT, J = C::J;
@@ -376,6 +391,27 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     compute_taps(tid);
   };
   if (conv_role) compute_taps(tid0);  // (visible behind the barrier that opens the first group of stars)
+  // C2 in the two-workgroup form (the kernel of P5's look-ahead): two waits of an iteration that no result depends on are off
+  // role 0's chain ("PSF fit: the serial head and tail of role 0's iteration").  Every other instantiation keeps the
+  // statements and the registers it had.
+  // * Role 0 stores its half straight behind P5: the stores need the thread's own gB and nothing else (header comment).
+  // * T of the next iteration is written behind the pixel step, so the closing barrier opens the first group of stars: that
+  //   group's own barrier goes (the tap tables were published by the barrier behind the poll); later groups keep theirs, V is
+  //   reused.  tpix, T at the thread's own pixels, lives from there to P5 of the next iteration.
+  constexpr bool TRIM = SPLIT && C::WC && PX == 8 && LC_SERIAL_TRIM;
+  static_assert(!TRIM || 3 * C::MAXS <= kWave, "the x0 sums and the stars' step are lanes of one wave");
+  [[maybe_unused]] float tpix_next[TRIM ? PX : 1];
+  if constexpr (TRIM) {
+    if (role == 0) {
+      const int pu = tid0 / (N / PX), pv = (tid0 % (N / PX)) * PX;
+#pragma unroll
+      for (int p = 0; p < PX; ++p) {
+        tpix_next[p] = Bp[p] + Tp[p];
+        T[pu * C::TSA + C::AP + pv + p] = tpix_next[p];
+      }
+    }
+    __syncthreads();  // T and the first tap tables
+  }
   // (measured and left out: s_setprio 1 for the second-dispatched half of the workgroup - MI355X_MICROARCH.md, two waves per
   //  SIMD - C2 16.2 us per iteration with and without, C3 shard 86.8 / 86.9)
   for (int it = 0; it < A.n_iter; ++it) {
@@ -400,7 +436,10 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     float tpix[PX];  // T at the thread's own pixels (WC layout)
     if (conv_role) {
     // ---- P1: T = Moffat + B into LDS -----------------------------------------------------
-    if (C::WC && STATE_REGS) {
+    if constexpr (TRIM) {  // (written behind the pixel step of the iteration before, or in front of the loop)
+#pragma unroll
+      for (int p = 0; p < PX; ++p) tpix[p] = tpix_next[p];
+    } else if (C::WC && STATE_REGS) {
 #pragma unroll
       for (int p = 0; p < PX; ++p) {
         tpix[p] = Bp[p] + Tp[p];
@@ -425,7 +464,9 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     // (the tap tables of this iteration were made at the end of the previous one, behind the star update: compute_taps)
 
     for (int g0 = 0; g0 < S; g0 += SG) {
-      __syncthreads();  // T and taps visible; previous group's P5 (reads V) done before P2 rewrites R
+      // T and taps visible; previous group's P5 (reads V) done before P2 rewrites R
+      // (TRIM: the closing barrier of the iteration before, or the one in front of the loop, has opened the first group)
+      if (!TRIM || g0 > 0) __syncthreads();
       LC_STAMP(1 + 5 * (g0 / SG));
       if constexpr (C::WC) {
         // ---- wave tasks: (star, block of JB down-sampled columns), everything up to V inside the wave ----
@@ -1023,7 +1064,25 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       for (int p = 0; p < PX; ++p) gB[p] += A.ext_grad[gpix + p];
     }
     }  // conv_role
-    __syncthreads();
+    if constexpr (TRIM) {
+      if (role == 0) {
+        LC_STAMP(41);
+        // role 0's half, straight from P5 (the choice of store as in the hand-off below)
+        float *mine = A.xch + (((size_t)f * 2 + (it & 1)) * 2 + 0) * (N * N + 64);
+#pragma unroll
+        for (int q = 0; q < PX / 4; ++q) {
+          lc_v4f v;
+          v.x = gB[4 * q];
+          v.y = gB[4 * q + 1];
+          v.z = gB[4 * q + 2];
+          v.w = gB[4 * q + 3];
+          if (same_xcd) store_plain_x4(mine + pu * N + pv + 4 * q, v);
+          else store_sc1_x4(mine + pu * N + pv + 4 * q, v);
+        }
+        if (tid == 0 && it == 0) store_sc1_f(mine + N * N + 1, __int_as_float(my_xcc + 1));
+      }
+    }
+    __syncthreads();  // (TRIM, role 0: the only barrier between P5 and the drain - REDX and SGR visible to the first wave)
     LC_STAMP(40);
     {
       if (conv_role && tid < S) {  // dchi2/dx0 of every star: the waves' partial sums in fixed order
@@ -1068,11 +1127,13 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     }
     LC_STAMP(42);
     // ---- loss ------------------------------------------------------------------------------
-    {
-      const float wl = wave_sum(l1);
-      if (lane == 0) REDW[wid] = wl;
+    if (!TRIM || role == 1) {  // (TRIM: role 0's l1 is identically zero, and its stores are out already: no sum, no barrier)
+      {
+        const float wl = wave_sum(l1);
+        if (lane == 0) REDW[wid] = wl;
+      }
+      __syncthreads();
     }
-    __syncthreads();
     float tl1 = 0.f;
     if (tid == 0 && starlet_role)
       for (int w = 0; w < C::NW; ++w) tl1 += REDW[w];
@@ -1086,6 +1147,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       // never moves) share an L2: plain stores keep their lines there and the partner's L1-bypassing loads are served from
       // it, where an sc1 store drops the line and the partner reads at the memory-side rate (MI355X_MICROARCH.md, "stores
       // of each flavour").  Anything else - another XCD, the first iteration, xcd_fast off - takes the sc1 stores.
+      if (!TRIM || role == 1) {  // (TRIM: role 0 stored its half and its XCD word behind P5)
 #pragma unroll
       for (int q = 0; q < PX / 4; ++q) {
         lc_v4f v;
@@ -1101,6 +1163,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         else store_sc1_f(mine + N * N, tl1);
       }
       if (tid == 0 && it == 0) store_sc1_f(mine + N * N + 1, __int_as_float(my_xcc + 1));
+      }
       // role 0: the stars' step needs nothing from the partner: done (by the first wave) while the stores drain.  The next tap
       // tables, which need that step, wait until the flag is up (below): in front of it they were ~1.5 k cycles by which role 0,
       // the longer role, published late.
@@ -1108,6 +1171,8 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       //  82.4 / 82.4 and 82.9, 83.3 / 82.6, 82.6 us per iteration with the late tables against without: the old order stays there)
       constexpr bool TAPS_LATE = STATE_REGS;
       if (role == 0 && A.mode == 1) {
+        // (TRIM: no workgroup barrier between the x0 sums and the step any more; both are lanes of the first wave, 3 S <= 64)
+        if constexpr (TRIM) wave_lds_sync();
         if (TAPS_LATE) step_stars(tid);
         else update_stars_and_taps(tid);
       }
@@ -1183,7 +1248,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       if (tid == 0 && role == 0) tl1 = (PX == 8) ? tl1_other : load_sc1_f(theirs + N * N);
       LC_STAMP(47);
     }
-    if (tid == 0 && conv_role) {
+    if (!TRIM && tid == 0 && conv_role) {  // (TRIM: in front of the closing barrier, below)
       float chi = 0.f;
       for (int s = 0; s < S; ++s) chi += SGR[s * 5];
       const float loss = 0.5f * chi + tl1;
@@ -1257,6 +1322,26 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         }
       }
       if constexpr (!SPLIT) update_stars_and_taps(tid);  // (the two-workgroup form did this beside its hand-off)
+    }
+    if constexpr (TRIM) {
+      if (role == 0) {  // T of the next iteration: B is final, and the last readers of T were this iteration's row passes
+#pragma unroll
+        for (int p = 0; p < PX; ++p) {
+          tpix_next[p] = Bp[p] + Tp[p];
+          T[pu * C::TSA + C::AP + pv + p] = tpix_next[p];
+        }
+        // the loss, as in the other forms.  Its store is the lane's last instruction in front of the barrier: ahead of the
+        // pixel step, the step's first wait on vmcnt (which the compiler places there for the state loaded in front of the
+        // loop) would be a wait for this store.
+        if (tid == 0) {
+          float chi = 0.f;
+          for (int s = 0; s < S; ++s) chi += SGR[s * 5];
+          const float loss = 0.5f * chi + tl1;
+          A.hist[(size_t)f * A.hist_stride + tglob] = loss;
+          if (A.out_loss) A.out_loss[f] = loss;
+          if (A.out_chi2) A.out_chi2[f] = chi;
+        }
+      }
     }
     __syncthreads();
     LC_STAMP(43);

@@ -22,9 +22,14 @@ out = (C.c_longlong * 128)()
 _lib.lib().lc_debug_get_stamps.argtypes = [C.POINTER(C.c_longlong)]
 assert _lib.lib().lc_debug_get_stamps(out) == 0
 allst = np.array(out[:], dtype=np.int64)
-names = {0: 'start', 1: 'P1 + taps (to first barrier)', 40: 'conv: wave tasks + P5', 42: 'starlet', 44: 'l1 reduce',
-         45: 'publish (stores, drain, barrier)', 46: 'flag, poll (role 0: + tap tables)', 47: 'read partner slab', 43: 'loss + update'}
-order = [0, 1, 40, 42, 44, 45, 46, 47, 43]
+# a segment is named after the stamp that ends it.  Stamp 41 exists only in role 0 of the C2 two-workgroup kernel (TRIM in
+# csrc/psf_kernels.h): there the hand-off stores come straight behind P5, in front of the barrier that stamp 40 follows, the
+# first group of stars has no opening barrier of its own (stamp 1 follows the loop top at once), role 0 runs neither starlet
+# nor l1 sum, and T of the next iteration and the loss are written in front of the closing barrier.
+names = {0: 'start', 1: 'P1 + taps (to first barrier; TRIM: loop top only)', 41: 'conv: wave tasks + P5 (to the first hand-off store)',
+         40: 'conv: wave tasks + P5, barrier', 42: 'starlet', 44: 'l1 reduce',
+         45: 'publish (stores, drain, barrier)', 46: 'flag, poll (role 0: + tap tables)', 47: 'read partner slab', 43: 'loss + update (TRIM: + T)'}
+order = [0, 1, 41, 40, 42, 44, 45, 46, 47, 43]
 for blk, label in ((0, 'block 0 (role 0 / single form)'), (64, 'block 8 (role 1)')):
     s = allst[blk:blk + 64]
     if s[43] == 0:
@@ -33,8 +38,10 @@ for blk, label in ((0, 'block 0 (role 0 / single form)'), (64, 'block 8 (role 1)
     keys = [k for k in order if s[k] != 0]
     tot = s[43] - s[0]
     prev = s[0]
+    trim = {40: 'hand-off stores issued, barrier', 42: 'x0 sums (no starlet)', 44: '(no l1 reduce)',
+            45: "x0 sums, stars' step, drain, barrier"} if s[41] else {}
     for k in keys[1:]:
-        print(f'  {names[k]:34s} {s[k]-prev:8d} ticks  {100*(s[k]-prev)/tot:5.1f}%')
+        print(f'  {trim.get(k, names[k]):34s} {s[k]-prev:8d} ticks  {100*(s[k]-prev)/tot:5.1f}%')
         prev = s[k]
     fine = {10: 'task start (prefetch issued)', 11: 'row pass', 12: 'column pass + reductions', 13: 'transposed column pass', 14: 'wave 0 done with its tasks', 15: 'barrier (other waves)', 16: 'per-star sums', 17: 'P5 transposed row pass'}
     if s[10]:

@@ -355,6 +355,38 @@ int lc_frames_cut_stamps(lc_frames *f, int S, int n, const int32_t *frame /*[S]*
                          float *data_out /*[S][n][n]*/, float *noisemap_out /*nullable*/, uint8_t *mask_out /*nullable*/,
                          int32_t *n_inside /*[S] nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- exact circular-aperture sums (photutils.aperture_photometry with CircularAperture, method='exact'), batched ------
+ * The reference takes the starting fluxes of the ROI's point sources from exact circular apertures on the median stack
+ * (lightcurver/processes/roi_modelling.py:198-204).  Here P apertures are summed in one call, one wave each (DESIGN.md
+ * section 5 "Aperture sums" is the SPEC; csrc/aperture.hip).  Aperture p lies on image image[p] (images in any order,
+ * repeated at will) with its centre at xy[p] = (x, y), x along the columns, 0-based with the pixel centres at integers,
+ * and has radius r[p].  The weight of a pixel is the area of its square inside the circle, in float64.  A pixel is good
+ * if it is in the image, not masked (mask != 0 excludes it) and its data and its error (when there is one) are finite.
+ *   sum       sum of weight * data over the good pixels
+ *   sum_err   sqrt(sum of weight * error^2) over the good pixels
+ *   area      sum of the weights of the good pixels
+ *   bad_area  sum of the weights of the bad pixels that are not masked
+ * A circle that lies outside the image gives four zeros.  An aperture's outputs depend on nothing but the aperture and its
+ * image: not on P, K, its place in the list or its neighbours, bit for bit.  kernel_ms = device time of the kernel (HIP
+ * events).
+ *   lc_aperture_sums         images, error map and mask are uploaded with the call.
+ *   lc_frames_aperture_sums  on the resident planes of a frame set (raw, or sub after an import); only the list is
+ *     uploaded.  with_error: the error of a pixel is the noise lc_frames_cut_stamps gives it, formed on the fly in the
+ *     same float32 steps from exptime and rms [K], each of which may be NULL after an import (the recorded values are
+ *     used).
+ * Checked on the host before anything is launched, the outputs untouched.  LC_ERR_INVALID: K, h, w or P < 1, a missing
+ * data, image, xy, r or sum, sum_err without an error source (error; with_error), an image index outside [0, K), a
+ * coordinate or radius that is not finite, r <= 0, with_error without exptime and rms (given or recorded), an exptime
+ * that is not finite or not > 0.  LC_ERR_UNSUPPORTED: lc_aperture_sums with K h w >= 2^31. */
+int lc_aperture_sums(lc_ctx *ctx, int K, int h, int w, const float *data /*[K][h][w]*/, const float *error /*nullable*/,
+                     const uint8_t *mask /*nullable*/, int P, const int32_t *image /*[P]*/, const double *xy /*[P][2]*/,
+                     const double *r /*[P]*/, double *sum /*[P]*/, double *sum_err /*[P] nullable*/,
+                     double *area /*[P] nullable*/, double *bad_area /*[P] nullable*/, float *kernel_ms /*nullable*/);
+int lc_frames_aperture_sums(lc_frames *f, int P, const int32_t *frame /*[P]*/, const double *xy, const double *r,
+                            const float *exptime /*[K], nullable after an import*/, const float *rms /*likewise*/,
+                            int with_error, double *sum, double *sum_err /*nullable*/, double *area /*nullable*/,
+                            double *bad_area /*nullable*/, float *kernel_ms /*nullable*/);
+
 /* ---- registration of source lists by star triangles (astroalign.find_transform), batched ----------------------------------
  * The reference gives a frame its WCS from another frame's, or from Gaia positions, with one astroalign.find_transform per
  * frame (lightcurver/processes/alternate_plate_solving_adapt_existing_wcs.py:24, alternate_plate_solving_with_gaia.py:66).

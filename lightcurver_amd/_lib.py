@@ -153,6 +153,9 @@ SIGNATURES = {
     'lc_cutout_supported': (C.c_int, [C.c_int, C.c_int]),
     'lc_frames_cut_stamps': (C.c_int, [vp, C.c_int, C.c_int, ip, ip, ip, fp, fp, C.c_int, C.c_int, C.POINTER(CosmicsCfg),
                                        C.POINTER(CcdmaskCfg), fp, fp, C.POINTER(C.c_uint8), ip, C.POINTER(C.c_float)]),
+    'lc_aperture_sums': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_uint8), C.c_int, ip, dp, dp, dp, dp,
+                                   dp, dp, C.POINTER(C.c_float)]),
+    'lc_frames_aperture_sums': (C.c_int, [vp, C.c_int, ip, dp, dp, fp, fp, C.c_int, dp, dp, dp, dp, C.POINTER(C.c_float)]),
     'lc_register_supported': (C.c_int, [C.c_int]),
     'lc_register_sources': (C.c_int, [vp, C.c_int, C.c_int, dp, ip, dp, ip, C.POINTER(RegisterCfg), dp, ip, ip, ip, ip,
                                       C.POINTER(C.c_float)]),

@@ -17,20 +17,11 @@
 
 #include "device_call.h"
 #include "frame_steps.h"
+#include "frames_state.h"
 #include "lc_common.h"
 #include "mask_steps.h"
 #include "noise_pixel.h"
 #include "../../include/lcmi.h"
-
-struct lc_frames {
-  lc_ctx *ctx = nullptr;
-  int K = 0, h = 0, w = 0;
-  bool imported = false;
-  lc::DevPool pool;         // everything below
-  float *planes = nullptr;  // [K][h][w]: the raw frames, sub after the import
-  float *sub = nullptr;     // [K][h][w]: the import's output until it takes the place of planes
-  float *exptime = nullptr, *rms = nullptr;  // [K]: recorded by the import
-};
 
 namespace lc {
 

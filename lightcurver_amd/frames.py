@@ -18,6 +18,13 @@ _i32p = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
 
 
+def _per_frame(values, K):
+    """One float32 per frame of the set from one value or K of them; None stays None."""
+    if values is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(values, np.float32).reshape(-1), (K,)), dtype=np.float32)
+
+
 class FrameSet:
     """K frames of one shape on the device.  ``stack``: (K, h, w), in electrons per second.  Raises without a device:
     there is no CPU fallback."""
@@ -107,13 +114,7 @@ class FrameSet:
             raise _lib.LcError(f'lc_frames_cut_stamps takes stamps of 8 .. 128 pixels with masks, any size with '
                                f'S n n < 2^31 without, not {S} of {n}')
         ccfg, bcfg = _mask_settings(dict(cosmics_masking_params or {}))
-
-        def per_frame(values):
-            if values is None:
-                return None
-            return np.ascontiguousarray(np.broadcast_to(np.asarray(values, np.float32).reshape(-1), (K,)), dtype=np.float32)
-
-        t, rms = per_frame(exptimes), per_frame(background_rms)
+        t, rms = _per_frame(exptimes, K), _per_frame(background_rms, K)
         if t is not None and not (np.isfinite(t) & (t > 0)).all():
             raise ValueError('exposure times must be finite and > 0')
         data = np.empty((S, n, n), np.float32)
@@ -127,6 +128,34 @@ class FrameSet:
             mask.ctypes.data_as(_u8p), inside.ctypes.data_as(_i32p), C.byref(ms)), 'lc_frames_cut_stamps')
         return dict(data=data, noisemap=noise, mask=mask.astype(bool), origin=origin, center_original=centre,
                     n_inside=inside, kernel_ms=ms.value)
+
+    def aperture_photometry(self, frame_index, positions_xy, r, with_error=False, exptimes=None, background_rms=None):
+        """P exact circular-aperture sums on the resident planes in one device call (``lc_frames_aperture_sums``; DESIGN.md
+        section 5 "Aperture sums").  frame_index: (P,) or one frame for all; positions_xy: (P, 2) pixel positions (x, y);
+        r: (P,) or one radius for all.  ``with_error``: the per-pixel error is the noise map ``cut_stamps`` would form,
+        from exptimes and background_rms (one per frame of the set, or one for all; after ``import_frames`` both default
+        to the recorded values).  Returns the dict of ``photutils.aperture_sums_batch``: sum, sum_err (None without
+        ``with_error``), area, bad_area float64 (P,), kernel_ms."""
+        from .photutils import _aperture_list
+        handle = self._handle()
+        K = self.shape[0]
+        frame, xy, rr = _aperture_list(K, frame_index, positions_xy, r)
+        P = len(xy)
+        out = dict(sum=np.zeros(P), sum_err=np.zeros(P) if with_error else None, area=np.zeros(P), bad_area=np.zeros(P),
+                   kernel_ms=0.0)
+        if not P:
+            return out
+        t, rms = _per_frame(exptimes, K), _per_frame(background_rms, K)
+        if t is not None and not (np.isfinite(t) & (t > 0)).all():
+            raise ValueError('exposure times must be finite and > 0')
+        dptr = lambda a: None if a is None else a.ctypes.data_as(_lib.dp)
+        ms = C.c_float()
+        self.ctx.check(self._l.lc_frames_aperture_sums(
+            handle, P, frame.ctypes.data_as(_i32p), dptr(xy), dptr(rr), ptr(t), ptr(rms), int(bool(with_error)),
+            dptr(out['sum']), dptr(out['sum_err']), dptr(out['area']), dptr(out['bad_area']), C.byref(ms)),
+            'lc_frames_aperture_sums')
+        out['kernel_ms'] = ms.value
+        return out
 
     def close(self):
         if getattr(self, 'h', None):

@@ -40,9 +40,19 @@ def _median_stack(data):
     return (0.5 * (s[:, (E - 1) // 2] + s[:, E // 2])).reshape(data.shape[1:])
 
 
-def initial_point_source_fluxes(data, xs, ys, radius):
+def initial_point_source_fluxes(data, xs, ys, radius, method='center', ctx=None):
     """Aperture sums on the median stack (roi_modelling.py:198-204 uses photutils' exact circular
-    apertures; this is the pixel-centre version, good enough for a starting point)."""
+    apertures).  ``method='center'``: the pixel-centre version on the host, good enough for a starting point;
+    ``'exact'``: the reference's exact circle / pixel overlaps, median stack (``median_stack_batch``) and sums
+    (``photutils.aperture_sums_batch``; DESIGN.md section 5 "Aperture sums") both on the device ``ctx``, in float32 data
+    with float64 weights.  Bad pixels count as zero in both."""
+    if method == 'exact':
+        from ..photutils import aperture_sums_batch
+        stack = median_stack_batch(np.asarray(data, dtype=np.float32)[None], ctx=ctx)
+        xy = np.stack([np.atleast_1d(np.asarray(xs, np.float64)), np.atleast_1d(np.asarray(ys, np.float64))], axis=1)
+        return [float(v) for v in aperture_sums_batch(stack, 0, xy, float(radius), ctx=ctx)['sum']]
+    if method != 'center':
+        raise ValueError(f"initial_point_source_fluxes: method must be 'center' or 'exact', not {method!r}")
     stack = _median_stack(data)
     n = stack.shape[0]
     yy, xx = np.mgrid[0:n, 0:n]
@@ -53,9 +63,10 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
                       initial_a=None, aperture_radius=3.0, fix_point_source_astrometry=False,
                       starting_background=None, further_optimize_background=True, regularization=None,
                       roi_deconv_translations_iters=300, roi_deconv_all_iters=2000, rescale=True,
-                      marginalize_positions=False):
+                      marginalize_positions=False, aperture_method='center'):
     """data, noisemap (E, n, n); psf (E, N, N); xs_pixels, ys_pixels: point-source positions in pixels of
-    the first epoch (0-based, as astropy's world_to_pixel returns them).
+    the first epoch (0-based, as astropy's world_to_pixel returns them).  ``aperture_method``: how the starting fluxes are
+    summed where ``initial_a`` is not given (``initial_point_source_fluxes``: 'center', or 'exact' as the reference).
 
     Returns a dict: kwargs_final, kwargs_stage1, loss_history (stage 2), loss_history_stage1, scale, model,
     and the pieces needed downstream (model object, kwargs_up / kwargs_down).  ``marginalize_positions``: also
@@ -81,7 +92,7 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
     else:
         angles = np.asarray(angles_to_north, dtype=np.float64) - float(np.asarray(angles_to_north)[0])
     if initial_a is None:
-        initial_a = initial_point_source_fluxes(data, xs, ys, aperture_radius)
+        initial_a = initial_point_source_fluxes(data, xs, ys, aperture_radius, method=aperture_method)
     offset = (n - 1) / 2.0  # STARRED's origin is the stamp centre
     c_x0, c_y0 = xs - offset, ys - offset
     model, k_init, k_up, k_down, _ = setup_model(data, noisemap ** 2, psf, c_x0, c_y0, subsampling_factor,
@@ -138,7 +149,8 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
     y_pix = np.array(k_final['kwargs_analytic']['c_y']) + np.array(k_final['kwargs_analytic']['dy'])[0] + offset
     out = dict(kwargs_final=k_final, kwargs_stage1=k_stage1, loss_history=optim2.loss_history,
                loss_history_stage1=optim1.loss_history, scale=scale, model=model, kwargs_up=k_up, kwargs_down=k_down,
-               data=data, noisemap=noisemap, x_pixels=x_pix, y_pixels=y_pix, W=W)
+               data=data, noisemap=noisemap, x_pixels=x_pix, y_pixels=y_pix, W=W,
+               initial_a=[float(v) for v in initial_a])
     if marginalize_positions:
         fisher = _polished_fisher(k_final, k_up, k_down, data, noisemap, model, 0, False, free_positions=True, prior=prior)
         cov, sx, sy = position_covariance_of(fisher)

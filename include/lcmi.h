@@ -654,6 +654,24 @@ typedef struct {                /* every pointer may be NULL; Lp = M + (flags & 
   float *sigma_a, *sigma_mean, *sigma_c; /* [E*M], [E], [2M] */
 } lc_fisher_positions_out;
 int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_out *out);
+/* Fisher information with the epochs' translations free: theta = (a [E * M], dx [E], dy [E], optionally mean [E] and c_x,
+ * c_y [M each]); alpha and h stay fixed.  The same arrowhead as lc_joint_fisher_positions with two more local parameters per
+ * epoch: the local block is ordered a_e (M), mean_e (0 / 1), dx_e, dy_e.  The columns of dx_e, dy_e hold the point sources
+ * (ss sum_i df/dX_i, df/dY_i) and the resampled background (the derivative of the bilinear resampling in the cell floor
+ * selects, clamped at the edge, as in the gradient of the loss), convolved with the epoch's PSF; the background pass runs
+ * whenever the object holds a background, whatever its values.  The flags are those of lc_joint_fisher_positions, the shifts
+ * are always free; the prior, the zero-diagonal rule, the 1e-6 pivot rule and the NaN outcome carry over.  Refusals as there
+ * (LC_ERR_INVALID: unknown flags, shared outputs without LC_FISHER_POSITIONS, sigma_mean without LC_FISHER_MEAN,
+ * LC_FISHER_PRIOR without LC_FISHER_POSITIONS; LC_ERR_UNSUPPORTED: a batched star-photometry object, LC_FISHER_PRIOR when
+ * the loss has no prior), and LC_ERR_UNSUPPORTED for LC_FISHER_POSITIONS without LC_FISHER_PRIOR: a common translation of
+ * all sources is a translation of every epoch, a gauge of the shifts, so with both free the information is exactly singular
+ * unless a background or a prior pins the frame - the call asks for the prior instead of leaving that to a pivot test on a
+ * float32 matrix.  Every refusal happens before a launch, outputs untouched. */
+typedef struct {  /* every pointer may be NULL; Lp = M + (flags & LC_FISHER_MEAN ? 1 : 0) + 2; local order a_e, mean_e, dx_e, dy_e */
+  float *F_local, *F_cross, *F_shared, *C_local, *C_cross, *C_shared;  /* [E][Lp][Lp], [E][Lp][2M], [2M][2M], twice */
+  float *sigma_a, *sigma_mean, *sigma_c, *sigma_dx, *sigma_dy;        /* [E*M], [E], [2M], [E], [E] */
+} lc_fisher_shifts_out;
+int lc_joint_fisher_shifts(lc_joint *j, int flags, const lc_fisher_shifts_out *out);
 /* Multi-GPU epoch sharding: split one optimiser step around the caller's all-reduce of the shared block
  * [dL/dh (N*N) | dL/dc_x (M) | dL/dc_y (M) | sum_e (a - ref) (M) | sum_e (a - ref)^2 (M) | chi2 | n_epochs]
  * living in device memory.  The flux moments (flux-uniformity term, jnp.std over epochs in the reference:

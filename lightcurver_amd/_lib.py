@@ -87,6 +87,13 @@ class FisherPositionsOut(C.Structure):
     _fields_ = [(name, fp) for name in FISHER_POSITIONS_FIELDS]
 
 
+FISHER_SHIFTS_FIELDS = FISHER_POSITIONS_FIELDS + ('sigma_dx', 'sigma_dy')
+
+
+class FisherShiftsOut(C.Structure):
+    _fields_ = [(name, fp) for name in FISHER_SHIFTS_FIELDS]
+
+
 class ExtractObject(C.Structure):
     _fields_ = [('first', C.c_int32), ('npix', C.c_int32), ('xmin', C.c_int32), ('xmax', C.c_int32), ('ymin', C.c_int32),
                 ('ymax', C.c_int32), ('xpeak', C.c_int32), ('ypeak', C.c_int32), ('flag', C.c_int32), ('pad', C.c_int32),
@@ -223,6 +230,7 @@ SIGNATURES = {
     'lc_joint_fisher_flux_sigma': (C.c_int, [vp, fp]),
     'lc_joint_fisher_flux_cov': (C.c_int, [vp, fp, fp, fp]),
     'lc_joint_fisher_positions': (C.c_int, [vp, C.c_int, C.POINTER(FisherPositionsOut)]),
+    'lc_joint_fisher_shifts': (C.c_int, [vp, C.c_int, C.POINTER(FisherShiftsOut)]),
     'lc_joint_step_local': (C.c_int, [vp]),
     'lc_joint_shared_buffer_dev': (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int)]),
     'lc_joint_step_update': (C.c_int, [vp, C.POINTER(AdabeliefCfg)]),

@@ -21,6 +21,11 @@
 // for c) is left out, sigma = +inf and zero rows / columns of C; a Cholesky pivot of any local block or of S that is not
 // above kFpPivot times its diagonal entry makes every C and sigma output NaN (F stays as computed).
 //
+// lc_joint_fisher_shifts (dx_e, dy_e free as well) runs the same three steps in their shifts mode: the local block is (a_e,
+// mean_e, dx_e, dy_e), the template kernel also leaves every source's ss a dT/dX, ss a dT/dY for the two new columns, which
+// joint_fisher_shifts.h writes before the Gram kernel, and the solve kernels are instantiated at the local capacity 11 beside 9.
+// With shifts = 0 nothing of the existing call changes: same columns, values and bits.
+//
 // joint_fit.hip includes this file for the argument structures and the launchers; the kernels themselves are compiled by
 // joint_fisher_positions.hip (LC_FISHER_POSITIONS_KERNELS), a translation unit of their own: the set of kernels of
 // joint_fit.hip and their registers are pinned by tests/test_psf_budget_isa_cpu.py.
@@ -34,11 +39,12 @@ namespace lc {
 constexpr int kFpMaxSources = 8;     // = kMaxSources (joint_kernels.h)
 constexpr double kFpPivot = 1e-6;    // = kFisherPivot (joint_fisher.h)
 
-constexpr int kFpCols = 32;      // columns of the slab: a (M), mean (0 / 1), c_x (M), c_y (M), zero padding
+constexpr int kFpCols = 32;      // columns of the slab: a (M), mean (0 / 1), [dx, dy,] c_x (M), c_y (M), zero padding
 constexpr int kFpThreads = 256;
 constexpr int kFpBand = 16;      // data rows per workgroup of the template kernel
 constexpr int kFpSpan = 24;      // table entries kept per source and axis at most (the 1e-30 cut leaves 21)
 constexpr int kFpLocal = kFpMaxSources + 1, kFpShared = 2 * kFpMaxSources;
+constexpr int kFpLocalShifts = kFpLocal + 2;  // lc_joint_fisher_shifts: a_e, mean_e, dx_e, dy_e
 constexpr float kFpCut = 1e-30f;
 
 struct FisherTmplArgs {
@@ -47,6 +53,11 @@ struct FisherTmplArgs {
   const float *a, *cx, *cy, *dx, *dy, *alpha;
   float *slab;       // [chunk][n n][32]
   int e0, M, n, ss, N, positions, mean;
+  // lc_joint_fisher_shifts: the local block is (a, mean, dx, dy) - two more columns ahead of c_x, c_y, written by
+  // joint_fisher_shift_cols_kernel (joint_fisher_shifts.h) - and every source leaves a ss dT/dX, a ss dT/dY of the scene
+  // frame, neither rotated nor weighted, in gsh [chunk][n n][2 M] for that kernel to add in source order
+  int shifts = 0;
+  float *gsh = nullptr;
 };
 
 inline size_t fisher_tmpl_lds(int n, int ss) {
@@ -62,14 +73,16 @@ struct FisherGramArgs {
 
 struct FisherArrowArgs {
   const double *Fd;    // [E][32][32]
-  double *Binv;        // [E][9][9]    F_loc^-1, zero rows / columns of the parameters left out
-  double *B;           // [E][9][16]   F_loc^-1 F_x
+  double *Binv;        // [E][KL][KL]  F_loc^-1, zero rows / columns of the parameters left out (KL = 9, with the shifts 11)
+  double *B;           // [E][KL][16]  F_loc^-1 F_x
   double *G;           // [E][16][16]  F_x^T B
   double *Ccc;         // [16][16]
   int *ok;             // [E + 1]: every epoch's factorisation, then the whole solve
   const float *prior;  // [4][M] (means and sigmas of c_x, c_y) or null
   int E, M, Lp, Sh;    // Sh = 2 M, or 0 with the positions fixed
   float *F_local, *F_cross, *F_shared, *C_local, *C_cross, *C_shared, *sigma_a, *sigma_mean, *sigma_c;
+  int shifts = 0;      // the last two local parameters are dx_e, dy_e (local capacity kFpLocalShifts)
+  float *sigma_dx = nullptr, *sigma_dy = nullptr;
 };
 
 // (joint_fisher_positions.hip) the template kernel on grid (bands, max(M, 1), epochs) with `lds` bytes; the Gram kernel on
@@ -87,7 +100,7 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_tmpl_kernel(FisherTmp
   __shared__ double XY[4];    // X, Y, cos, sin
   const int tid = threadIdx.x, band = blockIdx.x, i = blockIdx.y, b = blockIdx.z, e = A.e0 + b;
   const int n = A.n, ss = A.ss, N = A.N, M = A.M, nn = n * n;
-  const int Lp = M + (A.mean ? 1 : 0), P = Lp + (A.positions ? 2 * M : 0);
+  const int Lp = M + (A.mean ? 1 : 0) + (A.shifts ? 2 : 0), P = Lp + (A.positions ? 2 * M : 0);
   const int U0 = band * kFpBand, U1 = min(n, U0 + kFpBand);
   const int TL = N + ss;  // table stride (N + ss - 1 entries used)
   float *GXS = fp_lds, *DGXS = GXS + TL, *GYS = DGXS + TL, *DGYS = GYS + TL;
@@ -166,7 +179,7 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_tmpl_kernel(FisherTmp
   const int np = empty ? 0 : max(0, p1 - p0 + 1);  // <= ss kFpBand + kFpSpan - 1
   __syncthreads();
   const float *psf = A.psf + (size_t)e * N * N;
-  const bool pos = A.positions != 0;
+  const bool cpos = A.positions != 0, pos = cpos || A.shifts;  // the derivative passes; the c columns
   for (int idx = tid; idx < np * n; idx += kFpThreads) {  // row pass, block-summed over v
     const int pr = idx / n, V = idx % n;
     const float *kr = psf + (size_t)(p0 + pr) * N;
@@ -203,9 +216,14 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_tmpl_kernel(FisherTmp
     const float sw = sqrtf(w[px]);
     float *row = slab + (size_t)px * kFpCols;
     row[i] = sw * t;
-    if (pos) {
+    if (cpos) {
       row[Lp + i] = sw * amp * fs * (ca * gX + sa * gY);
       row[Lp + M + i] = sw * amp * fs * (ca * gY - sa * gX);
+    }
+    if (A.shifts) {
+      float *g = A.gsh + ((size_t)b * nn + px) * (2 * M) + 2 * i;
+      g[0] = amp * fs * gX;
+      g[1] = amp * fs * gY;
     }
   }
 }
@@ -281,11 +299,13 @@ __device__ bool fp_cholesky(const double (*S)[K], int m, double (*L)[K], double 
   return true;
 }
 
-// one workgroup per epoch: F_local, F_cross out; the local factorisation, B_e and F_x^T B_e
+// one workgroup per epoch: F_local, F_cross out; the local factorisation, B_e and F_x^T B_e.  KL: the capacity of the local
+// block (kFpLocal, or kFpLocalShifts with dx_e, dy_e), also the stride of Binv and B
+template <int KL>
 __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_local_kernel(FisherArrowArgs A) {
-  __shared__ double Fl[kFpLocal][kFpLocal], Fr[kFpLocal][kFpLocal], Ld[kFpLocal][kFpLocal], Li[kFpLocal][kFpLocal];
-  __shared__ double Inv[kFpLocal][kFpLocal], Fx[kFpLocal][kFpShared], Bs[kFpLocal][kFpShared];
-  __shared__ int IDX[kFpLocal], MM[2];
+  __shared__ double Fl[KL][KL], Fr[KL][KL], Ld[KL][KL], Li[KL][KL];
+  __shared__ double Inv[KL][KL], Fx[KL][kFpShared], Bs[KL][kFpShared];
+  __shared__ int IDX[KL], MM[2];
   const int e = blockIdx.x, tid = threadIdx.x, Lp = A.Lp, Sh = A.Sh;
   const double *F = A.Fd + (size_t)e * kFpCols * kFpCols;
   for (int k = tid; k < Lp * Lp; k += kFpThreads) {
@@ -306,16 +326,16 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_local_kernel(Fi
     for (int r = 0; r < m; ++r)
       for (int c = 0; c < m; ++c) Fr[r][c] = Fl[IDX[r]][IDX[c]];
     MM[0] = m;
-    MM[1] = fp_cholesky<kFpLocal>(Fr, m, Ld, Li) ? 1 : 0;
+    MM[1] = fp_cholesky<KL>(Fr, m, Ld, Li) ? 1 : 0;
     A.ok[e] = MM[1];
   }
   __syncthreads();
   const int m = MM[0];
   const bool ok = MM[1] != 0;
-  double *Bo = A.B + (size_t)e * kFpLocal * kFpShared, *Io = A.Binv + (size_t)e * kFpLocal * kFpLocal;
+  double *Bo = A.B + (size_t)e * KL * kFpShared, *Io = A.Binv + (size_t)e * KL * KL;
   double *Go = A.G + (size_t)e * kFpShared * kFpShared;
-  for (int k = tid; k < kFpLocal * kFpLocal; k += kFpThreads) Io[k] = 0.0;
-  for (int k = tid; k < kFpLocal * kFpShared; k += kFpThreads) Bo[k] = 0.0;
+  for (int k = tid; k < KL * KL; k += kFpThreads) Io[k] = 0.0;
+  for (int k = tid; k < KL * kFpShared; k += kFpThreads) Bo[k] = 0.0;
   for (int k = tid; k < kFpShared * kFpShared; k += kFpThreads) Go[k] = 0.0;
   if (!ok) return;
   __syncthreads();
@@ -324,7 +344,7 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_local_kernel(Fi
     double s = 0.0;
     for (int k = (r > c ? r : c); k < m; ++k) s += Li[k][r] * Li[k][c];
     Inv[r][c] = s;
-    Io[IDX[r] * kFpLocal + IDX[c]] = s;
+    Io[IDX[r] * KL + IDX[c]] = s;
   }
   __syncthreads();
   if (tid < m * Sh) {
@@ -397,12 +417,13 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_shared_kernel(F
 }
 
 // one workgroup per epoch: C_x = -B C_cc, C_loc = F_loc^-1 + B C_cc B^T, the local sigmas
+template <int KL>
 __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_back_kernel(FisherArrowArgs A) {
-  __shared__ double Cx[kFpLocal][kFpShared];
+  __shared__ double Cx[KL][kFpShared];
   const int e = blockIdx.x, tid = threadIdx.x, Lp = A.Lp, Sh = A.Sh, M = A.M;
   const bool ok = A.ok[A.E] != 0;
   const float nan = __builtin_nanf("");
-  const double *B = A.B + (size_t)e * kFpLocal * kFpShared, *Inv = A.Binv + (size_t)e * kFpLocal * kFpLocal;
+  const double *B = A.B + (size_t)e * KL * kFpShared, *Inv = A.Binv + (size_t)e * KL * KL;
   if (tid < Lp * Sh) {
     const int r = tid / Sh, c = tid % Sh;
     double s = 0.0;
@@ -413,13 +434,14 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_back_kernel(Fis
   __syncthreads();
   if (tid < Lp * Lp) {
     const int r = tid / Lp, c = tid % Lp;
-    double s = Inv[r * kFpLocal + c];
+    double s = Inv[r * KL + c];
     for (int k = 0; k < Sh; ++k) s -= Cx[r][k] * B[c * kFpShared + k];
     A.C_local[(size_t)e * Lp * Lp + tid] = ok ? (float)s : nan;
     if (r == c) {
       const bool out = !(A.Fd[(size_t)e * kFpCols * kFpCols + r * kFpCols + r] > 0.0);
       const float sg = !ok ? nan : (out ? __builtin_inff() : (float)sqrt(s));
       if (r < M) A.sigma_a[(size_t)e * M + r]  = sg;
+      else if (A.shifts && r >= Lp - 2) (r == Lp - 2 ? A.sigma_dx : A.sigma_dy)[e] = sg;
       else A.sigma_mean[e] = sg;
     }
   }

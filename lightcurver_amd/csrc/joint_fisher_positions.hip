@@ -12,10 +12,16 @@ void launch_fisher_gram(const FisherGramArgs &A, int epochs, hipStream_t q) {
   hipLaunchKernelGGL(joint_fisher_gram_kernel, dim3(epochs), dim3(kFpThreads), 0, q, A);
 }
 
-void launch_fisher_arrow(const FisherArrowArgs &A, hipStream_t q) {
-  hipLaunchKernelGGL(joint_fisher_arrow_local_kernel, dim3(A.E), dim3(kFpThreads), 0, q, A);
+template <int KL>
+static void launch_arrow(const FisherArrowArgs &A, hipStream_t q) {
+  hipLaunchKernelGGL(joint_fisher_arrow_local_kernel<KL>, dim3(A.E), dim3(kFpThreads), 0, q, A);
   hipLaunchKernelGGL(joint_fisher_arrow_shared_kernel, dim3(1), dim3(kFpThreads), 0, q, A);
-  hipLaunchKernelGGL(joint_fisher_arrow_back_kernel, dim3(A.E), dim3(kFpThreads), 0, q, A);
+  hipLaunchKernelGGL(joint_fisher_arrow_back_kernel<KL>, dim3(A.E), dim3(kFpThreads), 0, q, A);
+}
+
+void launch_fisher_arrow(const FisherArrowArgs &A, hipStream_t q) {
+  if (A.shifts) launch_arrow<kFpLocalShifts>(A, q);
+  else launch_arrow<kFpLocal>(A, q);
 }
 
 }  // namespace lc

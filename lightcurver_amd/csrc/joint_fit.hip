@@ -19,6 +19,7 @@
 #include "joint_lbfgs.h"
 #include "joint_fisher.h"
 #include "joint_fisher_positions.h"
+#include "joint_fisher_shifts.h"
 #include "noise_host.h"
 #include "starlet_norms.h"
 
@@ -174,6 +175,9 @@ struct lc_joint {
   double *fpos_work = nullptr;
   int *fpos_ok = nullptr;
   int fpos_chunk = 0;
+  // lc_joint_fisher_shifts (allocated on first use): the sources' shift derivatives [fpos_chunk][n*n][2 M] and the box-summed
+  // derivative fields of the background of one chunk (joint_fisher_shifts.h)
+  float *fsh_gsh = nullptr, *fsh_a2 = nullptr;
   DevPool pool;  // everything dmalloc handed out; hist, ghist and phist are grown and freed on their own
 };
 
@@ -2680,26 +2684,23 @@ int lc_joint_fisher_flux_cov(lc_joint *j, float *fisher, float *cov, float *sigm
   return LC_OK;
 }
 
-int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_out *out) {
-  if (!j || !out || (flags & ~(LC_FISHER_POSITIONS | LC_FISHER_MEAN | LC_FISHER_PRIOR))) return LC_ERR_INVALID;
-  LC_ENTER(j->ctx);
-  const bool positions = flags & LC_FISHER_POSITIONS, mean = flags & LC_FISHER_MEAN, prior = flags & LC_FISHER_PRIOR;
-  if (!positions && (out->F_cross || out->F_shared || out->C_cross || out->C_shared || out->sigma_c))
-    LC_FAIL(j->ctx, LC_ERR_INVALID, "lc_joint_fisher_positions: shared outputs need LC_FISHER_POSITIONS");
-  if (!mean && out->sigma_mean) LC_FAIL(j->ctx, LC_ERR_INVALID, "lc_joint_fisher_positions: sigma_mean needs LC_FISHER_MEAN");
-  if (prior && !positions) LC_FAIL(j->ctx, LC_ERR_INVALID, "lc_joint_fisher_positions: LC_FISHER_PRIOR needs LC_FISHER_POSITIONS");
-  if (j->G > 0)
-    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_positions: not available on a batched star-photometry object (positions are per star)");
-  if (prior && j->n_prior == 0) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_positions: LC_FISHER_PRIOR, but the loss has no prior on c_x, c_y");
+// lc_joint_fisher_positions and lc_joint_fisher_shifts behind their argument checks: the slab of every chunk of epochs, its
+// Gram matrices, the arrowhead solve and the outputs.  `shifts`: dx_e, dy_e are local parameters too (out->sigma_dx, sigma_dy).
+static int fisher_arrowhead(lc_joint *j, const char *who, bool shifts, bool positions, bool mean, bool prior,
+                            const lc_fisher_shifts_out *out) {
   const int E = j->E, M = j->M, n = j->n, nn = n * n;
   if (E == 0) return LC_OK;
-  const int Lp = M + (mean ? 1 : 0), Sh = positions ? 2 * M : 0;
+  const int Lp = M + (mean ? 1 : 0) + (shifts ? 2 : 0), Sh = positions ? 2 * M : 0;
   const size_t lds = fisher_tmpl_lds(n, j->ss);
-  if (lds > 64 * 1024) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_positions: stamp size beyond the template kernel's LDS");
-  // outputs at their largest (mean and positions free), one after the other
-  const size_t LM = (size_t)M + 1, SM = 2 * (size_t)M;
-  const size_t cap = 2 * ((size_t)E * LM * LM + (size_t)E * LM * SM + SM * SM) + (size_t)E * M + E + SM;
-  constexpr size_t kPerEpoch = kFpCols * kFpCols + kFpLocal * kFpLocal + kFpLocal * kFpShared + kFpShared * kFpShared;
+  if (lds > 64 * 1024) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, std::string(who) + ": stamp size beyond the template kernel's LDS");
+  if (shifts && j->ss != 1 && j->ss != 2)
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, std::string(who) + ": the background pass exists at subsampling 1 and 2");
+  // outputs at their largest (mean, shifts and positions free), one after the other; the work space at the larger local capacity
+  const size_t LM = (size_t)M + 3, SM = 2 * (size_t)M;
+  const size_t cap = 2 * ((size_t)E * LM * LM + (size_t)E * LM * SM + SM * SM) + (size_t)E * M + 3 * (size_t)E + SM;
+  constexpr size_t kPerEpoch =
+      kFpCols * kFpCols + kFpLocalShifts * kFpLocalShifts + kFpLocalShifts * kFpShared + kFpShared * kFpShared;
+  const size_t KL = shifts ? kFpLocalShifts : kFpLocal;
   if (!j->fpos_slab) {  // epochs per chunk: a slab of about 64 MiB
     const size_t per = (size_t)kFpCols * nn * sizeof(float);
     j->fpos_chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)E, ((size_t)64 << 20) / per));
@@ -2709,12 +2710,19 @@ int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_
     if (!rc) rc = dmalloc(j, &j->fpos_ok, (size_t)E + 1);
     if (rc) return rc;
   }
+  const float *h = j->par[LC_P_H];  // (no scan for zeros: an object that holds a background takes the background pass)
+  if (shifts && !j->fsh_gsh) {
+    int rc = dmalloc(j, &j->fsh_gsh, (size_t)j->fpos_chunk * nn * 2 * M);
+    // (zeroed by the allocation: the row of zeros at its start is never written)
+    if (!rc && h) rc = dmalloc(j, &j->fsh_a2, fisher_shift_a2_floats(j->fpos_chunk, n, j->ss));
+    if (rc) return rc;
+  }
   hipStream_t q = j->ctx->stream;
   FisherArrowArgs S{};
   S.Fd = j->fpos_work;
   S.Binv = j->fpos_work + (size_t)E * kFpCols * kFpCols;
-  S.B = S.Binv + (size_t)E * kFpLocal * kFpLocal;
-  S.G = S.B + (size_t)E * kFpLocal * kFpShared;
+  S.B = S.Binv + (size_t)E * KL * KL;
+  S.G = S.B + (size_t)E * KL * kFpShared;
   S.Ccc = S.G + (size_t)E * kFpShared * kFpShared;
   S.ok = j->fpos_ok;
   S.prior = prior ? j->prior : nullptr;
@@ -2722,6 +2730,7 @@ int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_
   S.M = M;
   S.Lp = Lp;
   S.Sh = Sh;
+  S.shifts = shifts ? 1 : 0;
   const size_t nFl = (size_t)E * Lp * Lp, nFx = (size_t)E * Lp * Sh, nFs = (size_t)Sh * Sh;
   S.F_local = j->fpos_out;
   S.F_cross = S.F_local + nFl;
@@ -2732,14 +2741,26 @@ int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_
   S.sigma_a = S.C_shared + nFs;
   S.sigma_mean = S.sigma_a + (size_t)E * M;
   S.sigma_c = S.sigma_mean + E;
-  const size_t used = (size_t)(S.sigma_c + Sh - j->fpos_out);
+  S.sigma_dx = S.sigma_c + Sh;
+  S.sigma_dy = S.sigma_dx + (shifts ? E : 0);
+  const size_t used = (size_t)(S.sigma_dy + (shifts ? E : 0) - j->fpos_out);
   const int bands = (n + kFpBand - 1) / kFpBand;
   for (int e0 = 0; e0 < E; e0 += j->fpos_chunk) {
     const int e1 = std::min(E, e0 + j->fpos_chunk);
     FisherTmplArgs T{j->psf_dev, j->wgt, j->par[LC_P_A], j->par[LC_P_CX], j->par[LC_P_CY], j->par[LC_P_DX], j->par[LC_P_DY],
                      j->par[LC_P_ALPHA], j->fpos_slab, e0, M, n, j->ss, j->N, positions ? 1 : 0, mean ? 1 : 0};
+    if (shifts) {
+      T.shifts = 1;
+      T.gsh = j->fsh_gsh;
+    }
     launch_fisher_tmpl(T, bands, std::max(M, 1), e1 - e0, lds, q);
     LC_HIP(j->ctx, hipGetLastError());
+    if (shifts) {
+      FisherShiftArgs H{j->psf_dev, j->wgt, h, j->par[LC_P_DX], j->par[LC_P_DY], j->par[LC_P_ALPHA], j->fsh_gsh, j->fsh_a2,
+                        j->fpos_slab, e0, M, n, j->ss, j->N, M + (mean ? 1 : 0)};
+      launch_fisher_shift_cols(H, e1 - e0, q);
+      LC_HIP(j->ctx, hipGetLastError());
+    }
     FisherGramArgs Gm{j->fpos_slab, nn, j->fpos_work + (size_t)e0 * kFpCols * kFpCols};
     launch_fisher_gram(Gm, e1 - e0, q);
     LC_HIP(j->ctx, hipGetLastError());
@@ -2761,7 +2782,45 @@ int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_
   give(out->sigma_a, S.sigma_a, (size_t)E * M);
   give(out->sigma_mean, S.sigma_mean, mean ? (size_t)E : 0);
   give(out->sigma_c, S.sigma_c, (size_t)Sh);
+  give(out->sigma_dx, S.sigma_dx, shifts ? (size_t)E : 0);
+  give(out->sigma_dy, S.sigma_dy, shifts ? (size_t)E : 0);
   return LC_OK;
+}
+
+// the argument errors the two calls share (LC_ERR_INVALID first, then LC_ERR_UNSUPPORTED), all before any launch
+static int fisher_arrowhead_check(lc_joint *j, const std::string &who, bool positions, bool mean, bool prior,
+                                  const lc_fisher_shifts_out *out) {
+  if (!positions && (out->F_cross || out->F_shared || out->C_cross || out->C_shared || out->sigma_c))
+    LC_FAIL(j->ctx, LC_ERR_INVALID, who + ": shared outputs need LC_FISHER_POSITIONS");
+  if (!mean && out->sigma_mean) LC_FAIL(j->ctx, LC_ERR_INVALID, who + ": sigma_mean needs LC_FISHER_MEAN");
+  if (prior && !positions) LC_FAIL(j->ctx, LC_ERR_INVALID, who + ": LC_FISHER_PRIOR needs LC_FISHER_POSITIONS");
+  if (j->G > 0)
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, who + ": not available on a batched star-photometry object (positions are per star)");
+  if (prior && j->n_prior == 0) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, who + ": LC_FISHER_PRIOR, but the loss has no prior on c_x, c_y");
+  return LC_OK;
+}
+
+int lc_joint_fisher_positions(lc_joint *j, int flags, const lc_fisher_positions_out *out) {
+  if (!j || !out || (flags & ~(LC_FISHER_POSITIONS | LC_FISHER_MEAN | LC_FISHER_PRIOR))) return LC_ERR_INVALID;
+  LC_ENTER(j->ctx);
+  const bool positions = flags & LC_FISHER_POSITIONS, mean = flags & LC_FISHER_MEAN, prior = flags & LC_FISHER_PRIOR;
+  const lc_fisher_shifts_out all{out->F_local, out->F_cross, out->F_shared, out->C_local, out->C_cross, out->C_shared,
+                                 out->sigma_a, out->sigma_mean, out->sigma_c, nullptr, nullptr};
+  if (int rc = fisher_arrowhead_check(j, "lc_joint_fisher_positions", positions, mean, prior, &all)) return rc;
+  return fisher_arrowhead(j, "lc_joint_fisher_positions", false, positions, mean, prior, &all);
+}
+
+int lc_joint_fisher_shifts(lc_joint *j, int flags, const lc_fisher_shifts_out *out) {
+  if (!j || !out || (flags & ~(LC_FISHER_POSITIONS | LC_FISHER_MEAN | LC_FISHER_PRIOR))) return LC_ERR_INVALID;
+  LC_ENTER(j->ctx);
+  const bool positions = flags & LC_FISHER_POSITIONS, mean = flags & LC_FISHER_MEAN, prior = flags & LC_FISHER_PRIOR;
+  if (int rc = fisher_arrowhead_check(j, "lc_joint_fisher_shifts", positions, mean, prior, out)) return rc;
+  // the gauge: a common translation of all sources is a translation of the epochs, so with c_x, c_y and the shifts free
+  // the information is singular unless the prior holds the positions (decided here, not by a pivot of a float32 matrix)
+  if (positions && !prior)
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_shifts: LC_FISHER_POSITIONS needs LC_FISHER_PRIOR - a common translation "
+                                        "of the sources is a gauge of the epochs' shifts, and only the prior fixes it");
+  return fisher_arrowhead(j, "lc_joint_fisher_shifts", true, positions, mean, prior, out);
 }
 
 #ifdef LC_STAMPS

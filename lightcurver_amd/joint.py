@@ -242,6 +242,27 @@ class JointFit:
         self._chk(self._l.lc_joint_fisher_positions(self.h, flags, C.byref(out)), 'fisher_positions')
         return res
 
+    def fisher_shifts(self, positions=False, mean=False, prior=None):
+        """Fisher information with the epochs' translations free (lc_joint_fisher_shifts): theta = (a, dx, dy[, mean][, c_x,
+        c_y]), alpha and h fixed - the fluxes' errors marginal over the registration every fit of them frees.  The dict of
+        ``fisher_positions`` with a wider local block, a_e, mean_e, dx_e, dy_e (Lp = M + 2, with ``mean`` M + 3), plus
+        sigma_dx, sigma_dy (E,).  ``positions=True`` needs the Gaussian prior on c_x, c_y (``prior``: None - the one last
+        given to set_loss, if any): a common translation of the sources is a gauge of the shifts, and the library refuses
+        the combination without a prior.  The degenerate cases are those of ``fisher_positions``."""
+        if prior is None:
+            prior = bool(positions) and getattr(self, '_has_prior', False)
+        E, M = self.E, self.M
+        Lp, Sh = M + (1 if mean else 0) + 2, (2 * M if positions else 0)
+        shapes = {'F_local': (E, Lp, Lp), 'F_cross': (E, Lp, Sh), 'F_shared': (Sh, Sh), 'C_local': (E, Lp, Lp),
+                  'C_cross': (E, Lp, Sh), 'C_shared': (Sh, Sh), 'sigma_a': (E * M,), 'sigma_mean': (E if mean else 0,),
+                  'sigma_c': (Sh,), 'sigma_dx': (E,), 'sigma_dy': (E,)}
+        res = {k: np.zeros(shapes[k], np.float32) for k in _lib.FISHER_SHIFTS_FIELDS}
+        out = _lib.FisherShiftsOut(*[ptr(res[k]) if res[k].size else None for k in _lib.FISHER_SHIFTS_FIELDS])
+        flags = ((_lib.FISHER_POSITIONS if positions else 0) | (_lib.FISHER_MEAN if mean else 0)
+                 | (_lib.FISHER_PRIOR if prior else 0))
+        self._chk(self._l.lc_joint_fisher_shifts(self.h, flags, C.byref(out)), 'fisher_shifts')
+        return res
+
     # multi-GPU split step (epoch sharding)
     def step_local(self):
         self._chk(self._l.lc_joint_step_local(self.h), 'step_local')
@@ -359,6 +380,9 @@ class StarPhotometryBatch(JointFit):
 
     def fisher_positions(self, positions=True, mean=False, prior=None):
         raise NotImplementedError('fisher_positions: the positions of a batched star photometry are per star')
+
+    def fisher_shifts(self, positions=False, mean=False, prior=None):
+        raise NotImplementedError('fisher_shifts: not built for a batched star photometry')
 
     def split(self, flat, name):
         """The concatenated block ``name`` as a list of per-star arrays."""

@@ -63,7 +63,7 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
                       initial_a=None, aperture_radius=3.0, fix_point_source_astrometry=False,
                       starting_background=None, further_optimize_background=True, regularization=None,
                       roi_deconv_translations_iters=300, roi_deconv_all_iters=2000, rescale=True,
-                      marginalize_positions=False, aperture_method='center'):
+                      marginalize_positions=False, aperture_method='center', marginalize_shifts=False):
     """data, noisemap (E, n, n); psf (E, N, N); xs_pixels, ys_pixels: point-source positions in pixels of
     the first epoch (0-based, as astropy's world_to_pixel returns them).  ``aperture_method``: how the starting fluxes are
     summed where ``initial_a`` is not given (``initial_point_source_fluxes``: 'center', or 'exact' as the reference).
@@ -73,9 +73,16 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
     ``astrometry_uncertainties`` = {'c_x_sigma', 'c_y_sigma' (M, data pixels), 'covariance' (2M, 2M; c_x, then c_y)} and
     ``fluxes_sigma`` (E * M, in the units of kwargs_final), from the Fisher information at the final point with the fluxes
     and the positions free (the astrometric prior of the fit included; conditional on dx, dy, alpha and h).
+    ``marginalize_shifts``: ``fluxes_sigma`` marginal over the epochs' translations dx, dy, which both stages fit, and
+    ``shift_uncertainties`` = {'dx_sigma', 'dy_sigma' (E, data pixels)}; combines with ``marginalize_positions``, which then
+    needs the astrometric prior (a float ``fix_point_source_astrometry``: a common translation of the sources is a gauge of
+    the shifts).
     """
     if marginalize_positions and isinstance(fix_point_source_astrometry, bool) and fix_point_source_astrometry:
         raise ValueError('marginalize_positions: the positions are fixed (fix_point_source_astrometry=True)')
+    if marginalize_positions and marginalize_shifts and not isinstance(fix_point_source_astrometry, float):
+        raise ValueError('marginalize_positions with marginalize_shifts needs the astrometric prior '
+                         '(fix_point_source_astrometry as a float)')
     reg = dict(DEFAULT_REGULARIZATION)
     reg.update(regularization or {})
     data = np.array(data, dtype=np.float64)
@@ -151,18 +158,24 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
                loss_history_stage1=optim1.loss_history, scale=scale, model=model, kwargs_up=k_up, kwargs_down=k_down,
                data=data, noisemap=noisemap, x_pixels=x_pix, y_pixels=y_pix, W=W,
                initial_a=[float(v) for v in initial_a])
-    if marginalize_positions:
-        fisher = _polished_fisher(k_final, k_up, k_down, data, noisemap, model, 0, False, free_positions=True, prior=prior)
-        cov, sx, sy = position_covariance_of(fisher)
-        out['astrometry_uncertainties'] = {'c_x_sigma': sx, 'c_y_sigma': sy, 'covariance': cov}
-        out['fluxes_sigma'] = np.array(fisher.get_kwargs_sigma()['kwargs_analytic']['a'], dtype=np.float64)
+    if marginalize_positions or marginalize_shifts:
+        fisher = _polished_fisher(k_final, k_up, k_down, data, noisemap, model, 0, False, free_positions=marginalize_positions,
+                                  prior=prior if marginalize_positions else None, free_shifts=marginalize_shifts)
+        sig = fisher.get_kwargs_sigma()['kwargs_analytic']
+        if marginalize_positions:
+            cov, sx, sy = position_covariance_of(fisher)
+            out['astrometry_uncertainties'] = {'c_x_sigma': sx, 'c_y_sigma': sy, 'covariance': cov}
+        if marginalize_shifts:
+            out['shift_uncertainties'] = {'dx_sigma': np.array(sig['dx'], dtype=np.float64),
+                                          'dy_sigma': np.array(sig['dy'], dtype=np.float64)}
+        out['fluxes_sigma'] = np.array(sig['a'], dtype=np.float64)
     return out
 
 
 def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pixels, initial_a, scale,
                               group=None, use_peer=False, regularization=None, roi_deconv_translations_iters=300,
                               roi_deconv_all_iters=2000, further_optimize_background=True, ctx=None,
-                              return_flux_covariance=False, marginalize_positions=False):
+                              return_flux_covariance=False, marginalize_positions=False, marginalize_shifts=False):
     """The two-stage fit of ``model_roi_cutouts`` with the epochs spread over the ranks of a torch.distributed group (one
     process per GPU): every rank passes ITS epochs - data, noisemap (E_local, n, n), psf (E_local, N, N) - and the same
     ``initial_a`` (M fluxes) and ``scale`` (nanmax of the data of ALL epochs: ``global_scale``).  The reference has no
@@ -176,9 +189,11 @@ def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels
     loss histories and the Fisher 1-sigma of the fluxes at the final point.  ``return_flux_covariance``: also the (E, M, M)
     covariance blocks of the fluxes of all epochs (``fluxes_covariance``: every rank its epochs', gathered in the order of
     ``fluxes_sigma``).  ``marginalize_positions`` is not built here (NotImplementedError): the Schur complement of the
-    positions sums over the epochs of all ranks."""
+    positions sums over the epochs of all ranks; ``marginalize_shifts`` neither."""
     if marginalize_positions:
         raise NotImplementedError('marginalize_positions in the sharded ROI fit: the Schur sum crosses the ranks')
+    if marginalize_shifts:
+        raise NotImplementedError('marginalize_shifts is not built in the sharded ROI fit')
     import torch
     import torch.distributed as dist
     from ..distributed import PeerGroup, ShardedJointOptimizer, gather_epoch_blocks, host_group
@@ -259,20 +274,27 @@ def global_scale(data, group=None):
 
 
 def fluxes_from_model(model, kwargs, kwargs_up, kwargs_down, data, noisemap, n_sources, model_scale,
-                      normalization_errors, marginalize_positions=False, prior=None):
+                      normalization_errors, marginalize_positions=False, prior=None, marginalize_shifts=False):
     """Numeric part of get_fluxes_dataframe_from_model (roi_modelling.py:450-474): per-source light
     curves (a is epoch-major: curve i = a[i::M]), their uncertainties (Fisher 1-sigma compounded with the
     frame normalisation error), residuals and the per-frame reduced chi2.  ``marginalize_positions``: the photon error is
     the marginal one with the fluxes and the positions c_x, c_y free (``prior``: the fit's ``Prior`` on them), and the
-    result gains ``astrometry_uncertainties`` = {'c_x_sigma', 'c_y_sigma', 'covariance'} (data pixels)."""
+    result gains ``astrometry_uncertainties`` = {'c_x_sigma', 'c_y_sigma', 'covariance'} (data pixels).
+    ``marginalize_shifts``: the photon error is marginal over the epochs' translations dx, dy (too; the positions beside
+    them need the ``prior``), and the result gains ``shift_uncertainties`` = {'dx_sigma', 'dy_sigma'} (data pixels)."""
     a = np.array(kwargs['kwargs_analytic']['a'])
-    astrometry = None
-    if marginalize_positions:
-        fisher = _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, 10, False, free_positions=True,
-                                  prior=prior)
-        sigma_a = np.array(fisher.get_kwargs_sigma()['kwargs_analytic']['a'], dtype=np.float64)
-        cov, sx, sy = position_covariance_of(fisher)
-        astrometry = {'c_x_sigma': sx, 'c_y_sigma': sy, 'covariance': cov}
+    astrometry = shifts = None
+    if marginalize_positions or marginalize_shifts:
+        fisher = _polished_fisher(kwargs, kwargs_up, kwargs_down, data, noisemap, model, 10, False,
+                                  free_positions=marginalize_positions, prior=prior if marginalize_positions else None,
+                                  free_shifts=marginalize_shifts)
+        sig = fisher.get_kwargs_sigma()['kwargs_analytic']
+        sigma_a = np.array(sig['a'], dtype=np.float64)
+        if marginalize_positions:
+            cov, sx, sy = position_covariance_of(fisher)
+            astrometry = {'c_x_sigma': sx, 'c_y_sigma': sy, 'covariance': cov}
+        if marginalize_shifts:
+            shifts = {'dx_sigma': np.array(sig['dx'], dtype=np.float64), 'dy_sigma': np.array(sig['dy'], dtype=np.float64)}
     else:
         sigma_a = np.array(get_flux_uncertainties(kwargs=kwargs, kwargs_up=kwargs_up, kwargs_down=kwargs_down,
                                                   data=data, noisemap=noisemap, model=model))
@@ -289,6 +311,8 @@ def fluxes_from_model(model, kwargs, kwargs_up, kwargs_down, data, noisemap, n_s
                reduced_chi2=np.array(chi2_per_frame))
     if astrometry is not None:
         out['astrometry_uncertainties'] = astrometry
+    if shifts is not None:
+        out['shift_uncertainties'] = shifts
     return out
 
 

@@ -9,7 +9,7 @@ from ..starred.deconvolution.loss import Loss
 from ..starred.deconvolution.parameters import ParametersDeconv
 from ..starred.optim.optimization import Optimizer
 from ..starred.utils.noise_utils import propagate_noise
-from ..utilities.starred_utilities import get_flux_uncertainties
+from ..utilities.starred_utilities import get_flux_covariance, get_flux_uncertainties
 
 
 def prepare_star_epochs(data, noisemap, cosmics_mask):
@@ -38,11 +38,14 @@ def _border_level(stack):
 
 
 def do_one_star_forward_modelling(data, noisemap, psf, subsampling_factor, n_iter=2000,
-                                  uniform_background_per_epoch=False, starlet_global_background=True):
+                                  uniform_background_per_epoch=False, starlet_global_background=True,
+                                  marginalize_shifts=False):
     """data, noisemap: (E, n, n) (rescaled IN PLACE by nanmax(data)); psf: (E, N, N) narrow PSFs.
 
     Returns dict: scale, kwargs_final, fluxes, fluxes_uncertainties, chi2, chi2_per_frame, loss_curve,
-    residuals, deconvolved_image, starlet_background.
+    residuals, deconvolved_image, starlet_background.  ``marginalize_shifts``: also ``fluxes_uncertainties_marginal`` (E,),
+    the 1-sigma of the fluxes marginal over the epochs' translations dx, dy the fit frees (and over ``mean`` where the fit
+    had it free); the star's position stays fixed there - it is the gauge of the shifts.
     """
     scale = np.nanmax(data)
     data /= scale
@@ -86,6 +89,11 @@ def do_one_star_forward_modelling(data, noisemap, psf, subsampling_factor, n_ite
     sigma_a = get_flux_uncertainties(kwargs=k_final, kwargs_down=k_down, kwargs_up=k_up, data=data,
                                      noisemap=noisemap, model=model)
     scene, background = model.getDeconvolved(k_final, 0)
+    extra = {}
+    if marginalize_shifts:
+        cov = get_flux_covariance(k_final, k_up, k_down, data, noisemap, model, free_shifts=True,
+                                  free_mean=bool(uniform_background_per_epoch))
+        extra['fluxes_uncertainties_marginal'] = scale * np.sqrt(cov[:, 0, 0])
     return {
         'scale': scale,
         'kwargs_final': k_final,
@@ -97,6 +105,7 @@ def do_one_star_forward_modelling(data, noisemap, psf, subsampling_factor, n_ite
         'residuals': scale * residuals,
         'deconvolved_image': scale * scene,
         'starlet_background': scale * background,
+        **extra,
     }
 
 

@@ -7,7 +7,11 @@ With the source positions (and optionally the epochs' means) free as well the in
 blocks (a_e, mean_e), one shared block (c_x, c_y) and the couplings - whose inverse comes from the Schur complement of the
 shared block: ``arrowhead_covariance`` is the float64 restatement of what the device computes
 (``JointFit.fisher_positions``), ``dense_from_arrowhead`` assembles dense matrices from the blocks.  Everything else (dx,
-dy, alpha, h) stays fixed: the result is conditional on the registration and the background."""
+dy, alpha, h) stays fixed: the result is conditional on the registration and the background.
+
+With the epochs' translations free too (``JointFit.fisher_shifts``) the local block grows by dx_e, dy_e - a_e, mean_e, dx_e,
+dy_e - and the same two functions take it with ``shifts=True``; the positions are then free only under a prior (a common
+translation of the sources is a gauge of the shifts)."""
 import numpy as np
 
 from ..deconvolution.deconvolution import nest_kwargs
@@ -16,6 +20,9 @@ PIVOT = 1e-6          # a Cholesky pivot not above PIVOT times its diagonal entr
 DENSE_LIMIT = 4096    # parameters beyond which dense_from_arrowhead refuses
 
 FREE_SETS = (['a'], ['a', 'mean'], ['a', 'c_x', 'c_y'], ['a', 'c_x', 'c_y', 'mean'])
+# ... and with the translations of the epochs free (both), in the order of the parameter class
+SHIFT_SETS = (['a', 'dx', 'dy'], ['a', 'dx', 'dy', 'mean'], ['a', 'c_x', 'c_y', 'dx', 'dy'],
+              ['a', 'c_x', 'c_y', 'dx', 'dy', 'mean'])
 
 
 def block_diagonal(blocks):
@@ -45,13 +52,16 @@ def _cholesky_inverse(S):
     return Li.T @ Li
 
 
-def arrowhead_covariance(F_local, F_cross, F_shared):
+def arrowhead_covariance(F_local, F_cross, F_shared, shifts=False):
     """Inverse of the arrowhead information in float64: ``F_local`` (E, Lp, Lp), ``F_cross`` (E, Lp, S), ``F_shared`` (S, S)
     (S may be 0) -> dict C_local, C_cross, C_shared of the same shapes, sigma_local (E, Lp), sigma_shared (S,), B (E, Lp, S).
       B_e = F_loc,e^-1 F_x,e;  S = F_cc - sum_e F_x,e^T B_e (epoch order);  C_cc = S^-1;  C_x,e = -B_e C_cc;
       C_loc,e = F_loc,e^-1 + B_e C_cc B_e^T;  cov(loc_e, loc_f) = B_e C_cc B_f^T for e != f (dense_from_arrowhead).
     A parameter whose diagonal entry is zero is left out (sigma = +inf, zero rows and columns of C); a Cholesky pivot of a
-    local block or of S that is not above 1e-6 times its diagonal entry makes every C and sigma NaN."""
+    local block or of S that is not above 1e-6 times its diagonal entry makes every C and sigma NaN.  ``shifts``: the local
+    block ends with dx_e, dy_e (the solve is the same; Lp must then be at least 2)."""
+    if shifts and np.shape(F_local)[1] < 2:
+        raise ValueError('local blocks with the shifts hold dx_e, dy_e at least')
     Fl = np.asarray(F_local, np.float64)
     E, Lp, _ = Fl.shape
     Fs = np.zeros((0, 0)) if F_shared is None else np.asarray(F_shared, np.float64)
@@ -94,9 +104,10 @@ def arrowhead_covariance(F_local, F_cross, F_shared):
     return res
 
 
-def dense_from_arrowhead(local, cross, shared, M, covariance=False):
+def dense_from_arrowhead(local, cross, shared, M, covariance=False, shifts=False):
     """Dense matrix of the arrowhead blocks in the order a (E * M, epoch-major), c_x, c_y, mean (E) - the order of
-    ``set_free``.  ``covariance=False``: the blocks are those of the information (different epochs do not couple);
+    ``set_free`` - then, with ``shifts`` (local blocks a_e, mean_e, dx_e, dy_e), dx (E), dy (E).
+    ``covariance=False``: the blocks are those of the information (different epochs do not couple);
     ``covariance=True``: those of its inverse, and the local parameters of two epochs e != f get
     C_x,e C_cc^-1 C_x,f^T (= B_e C_cc B_f^T).  ValueError above 4096 parameters."""
     local = np.asarray(local, np.float64)
@@ -104,7 +115,8 @@ def dense_from_arrowhead(local, cross, shared, M, covariance=False):
     shared = np.zeros((0, 0)) if shared is None else np.asarray(shared, np.float64)
     S = shared.shape[0]
     cross = np.zeros((E, Lp, S)) if cross is None or S == 0 else np.asarray(cross, np.float64).reshape(E, Lp, S)
-    if Lp not in (M, M + 1):
+    nsh = 2 if shifts else 0
+    if Lp - nsh not in (M, M + 1):
         raise ValueError(f'local blocks of {Lp} parameters for {M} sources')
     P = E * Lp + S
     if P > DENSE_LIMIT:
@@ -112,8 +124,13 @@ def dense_from_arrowhead(local, cross, shared, M, covariance=False):
     # position of local parameter (e, k) and of the shared ones in the dense order
     pos = np.empty((E, Lp), int)
     pos[:, :M] = np.arange(E * M).reshape(E, M)
-    if Lp > M:
+    has_mean = Lp - nsh > M
+    if has_mean:
         pos[:, M] = E * M + S + np.arange(E)
+    if shifts:
+        first = E * M + S + (E if has_mean else 0)
+        pos[:, Lp - 2] = first + np.arange(E)
+        pos[:, Lp - 1] = first + E + np.arange(E)
     sh = E * M + np.arange(S)
     D = np.zeros((P, P))
     D[np.ix_(sh, sh)] = shared
@@ -139,14 +156,17 @@ def dense_from_arrowhead(local, cross, shared, M, covariance=False):
 class FisherCovariance:
     """``free`` of the parameter class: ['a'] (the reference's use), ['a', 'mean'], ['a', 'c_x', 'c_y'] or
     ['a', 'c_x', 'c_y', 'mean'].  Beyond ['a'] the information comes from ``JointFit.fisher_positions`` (with the Gaussian
-    prior on c_x, c_y of the loss, if it has one), conditional on dx, dy, alpha and h."""
+    prior on c_x, c_y of the loss, if it has one), conditional on dx, dy, alpha and h.  Each of the four also with 'dx',
+    'dy' (both): ``JointFit.fisher_shifts``, conditional on alpha and h only; 'c_x', 'c_y' beside the shifts need the
+    prior (the library refuses them without)."""
 
     def __init__(self, param_class, optimizer_class, diagonal_only=True):
         free = list(param_class.free)
-        if free not in [list(f) for f in FREE_SETS]:
+        if free not in [list(f) for f in FREE_SETS + SHIFT_SETS]:
             raise NotImplementedError("Fisher information is built for the fluxes 'a', optionally with the positions "
-                                      "'c_x', 'c_y' (both) and / or 'mean' free")
+                                      "'c_x', 'c_y' (both), 'mean' and / or the shifts 'dx', 'dy' (both) free")
         self._free = free
+        self._shifts = 'dx' in free
         self._positions = 'c_x' in free
         self._mean = 'mean' in free
         self._param = param_class
@@ -169,8 +189,9 @@ class FisherCovariance:
             else:
                 self._F, self._C, self._sigma = fit.fisher_flux_covariance()
             return
-        self._arrow = fit.fisher_positions(positions=self._positions, mean=self._mean)
-        self._M = self._arrow['F_local'].shape[1] - (1 if self._mean else 0)
+        call = fit.fisher_shifts if self._shifts else fit.fisher_positions
+        self._arrow = call(positions=self._positions, mean=self._mean)
+        self._M = self._arrow['F_local'].shape[1] - (1 if self._mean else 0) - (2 if self._shifts else 0)
 
     def _sigmas(self):
         """name -> 1-sigma of the free blocks beyond ['a']."""
@@ -182,8 +203,12 @@ class FisherCovariance:
             out = {'a': loc[:, :M].reshape(-1)}
             if self._mean:
                 out['mean'] = loc[:, M]
+            if self._shifts:
+                out['dx'], out['dy'] = loc[:, -2], loc[:, -1]
         else:
             out = {'a': A['sigma_a'], 'mean': A['sigma_mean']}
+            if self._shifts:
+                out['dx'], out['dy'] = A['sigma_dx'], A['sigma_dy']
             sh = A['sigma_c']
         if self._positions:
             out['c_x'], out['c_y'] = sh[:M], sh[M:]
@@ -235,11 +260,12 @@ class FisherCovariance:
         A = self._arrow
         k = 'C' if covariance else 'F'
         return dense_from_arrowhead(A[k + '_local'], A[k + '_cross'] if self._positions else None,
-                                    A[k + '_shared'] if self._positions else None, self._M, covariance=covariance)
+                                    A[k + '_shared'] if self._positions else None, self._M, covariance=covariance,
+                                    shifts=self._shifts)
 
     @property
     def fisher_matrix(self):
-        """Dense Fisher information in the order a, c_x, c_y, mean of the free blocks ((E * M, E * M), block diagonal over the
+        """Dense Fisher information in the order a, c_x, c_y, mean, dx, dy of the free blocks ((E * M, E * M), block diagonal over the
         epochs, with only the fluxes free)."""
         F = self._blocks()[0]
         return block_diagonal(F) if self._flux_only else self._dense(False)

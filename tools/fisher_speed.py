@@ -3,7 +3,11 @@ information (fisher_flux_covariance: the same M launches writing the template sl
 back).  python tools/fisher_speed.py [reps] - at the C4 size (200 epochs of 64 x 64, M = 4) and one C5 shard (125 epochs of
 128 x 128, M = 8), background non-zero (the FFT epoch kernels) and zero (the point-source kernel where the size has one).
 Then the information with the positions free (fisher_positions: template kernel, Gram kernel on the matrix cores, the float64
-arrowhead solve, one copy back) beside the flux-only covariance, at 200 x 64 x 64 and 125 x 128 x 128 with M = 4."""
+arrowhead solve, one copy back) beside the flux-only covariance, at 200 x 64 x 64 and 125 x 128 x 128 with M = 4.
+Last the information with the epochs' shifts free (fisher_shifts: the same plus the background pass of the dx, dy columns)
+beside fisher_positions, at 200 x 64 x 64 with M = 2 and 125 x 128 x 128 with M = 4; the background pass on its own comes
+from a kernel trace of this script (rocprofv3 --kernel-trace --stats: joint_fisher_shift_field_kernel + ..._cols_kernel).
+python tools/fisher_speed.py [reps] shifts runs that last part alone."""
 import os
 import sys
 import time
@@ -16,8 +20,9 @@ from lightcurver_amd.joint import JointFit
 from lightcurver_amd.synthetic import make_roi_dataset
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+shifts_only = len(sys.argv) > 2 and sys.argv[2] == 'shifts'
 ctx = _lib.Context(0)
-for name, E, n, M in (('C4', 200, 64, 4), ('C5-shard', 125, 128, 8)):
+for name, E, n, M in () if shifts_only else (('C4', 200, 64, 4), ('C5-shard', 125, 128, 8)):
     ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=11, with_background=True)
     p = {k: np.asarray(v, np.float64) for k, v in ds['truth'].items()}
     for bg in (True, False):
@@ -40,7 +45,7 @@ for name, E, n, M in (('C4', 200, 64, 4), ('C5-shard', 125, 128, 8)):
         print(f'{name} E={E} n={n} M={M} background={"on " if bg else "off"}: diagonal {res["diagonal"]:.3f} ms, '
               f'covariance {res["covariance"]:.3f} ms, ratio {res["covariance"] / res["diagonal"]:.2f}', flush=True)
 
-for name, E, n, M in (('C4', 200, 64, 4), ('C5-shard', 125, 128, 4)):
+for name, E, n, M in () if shifts_only else (('C4', 200, 64, 4), ('C5-shard', 125, 128, 4)):
     ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=11, with_background=True)
     p = {k: np.asarray(v, np.float64) for k, v in ds['truth'].items()}
     j = JointFit(ds['data'], ds['noisemap'].astype(np.float64) ** 2, ds['psf'], 2, M, ctx)
@@ -62,3 +67,28 @@ for name, E, n, M in (('C4', 200, 64, 4), ('C5-shard', 125, 128, 4)):
         res[label] = float(np.median(t)) * 1e3
     j.close()
     print(f'{name} E={E} n={n} M={M}: ' + ', '.join(f'{k} {v:.3f} ms' for k, v in res.items()), flush=True)
+
+for name, E, n, M in (('C4', 200, 64, 2), ('C5-shard', 125, 128, 4)):
+    ds = make_roi_dataset(E=E, M=M, n=n, ss=2, seed=11, with_background=True)
+    p = {k: np.asarray(v, np.float64) for k, v in ds['truth'].items()}
+    j = JointFit(ds['data'], ds['noisemap'].astype(np.float64) ** 2, ds['psf'], 2, M, ctx)
+    j.set_params(**p)
+    j.set_free(['a'])
+    j.set_loss(prior={'c_x_mean': p['c_x'], 'c_x_sigma': np.full(M, 0.05), 'c_y_mean': p['c_y'], 'c_y_sigma': np.full(M, 0.05)})
+    calls = (('positions free', j.fisher_positions), ('fluxes only', lambda: j.fisher_positions(positions=False)),
+             ('shifts free', j.fisher_shifts), ('shifts + positions + mean free', lambda: j.fisher_shifts(positions=True, mean=True)))
+    for _, fn in calls:
+        fn()
+    ctx.synchronize()
+    res = {}
+    for label, fn in calls:
+        t = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            t.append(time.perf_counter() - t0)
+        res[label] = float(np.median(t)) * 1e3
+    j.close()
+    N = 2 * n
+    print(f'{name} E={E} n={n} M={M}: ' + ', '.join(f'{k} {v:.3f} ms' for k, v in res.items())
+          + f'; background pass: {2 * E * n * n * N * N / 1e9:.2f} G multiply-adds', flush=True)

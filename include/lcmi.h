@@ -672,6 +672,21 @@ typedef struct {  /* every pointer may be NULL; Lp = M + (flags & LC_FISHER_MEAN
   float *sigma_a, *sigma_mean, *sigma_c, *sigma_dx, *sigma_dy;        /* [E*M], [E], [2M], [E], [E] */
 } lc_fisher_shifts_out;
 int lc_joint_fisher_shifts(lc_joint *j, int flags, const lc_fisher_shifts_out *out);
+/* ... of a batched star-photometry object (lc_joint_create_groups, lc_joint_create_groups_background), every star in one
+ * call: theta = (a [sum E_g * M], dx, dy [sum E_g], optionally mean [sum E_g]); every star's c_x, c_y stay fixed (the gauge of
+ * that star's shifts), alpha and h too.  With the positions fixed the information is block diagonal over the epochs: the
+ * local block of an epoch is that of lc_joint_fisher_shifts (a_e, mean_e, dx_e, dy_e; Lp = M + mean + 2), computed with its
+ * own star's positions and, in a batch with backgrounds, its own star's h - bit for bit what lc_joint_fisher_shifts gives
+ * for a plain object over that star's epochs and parameters (for a batch without a background: one holding h = 0).  Outputs
+ * in the order the batch concatenates its stars, every pointer may be NULL; the shared outputs (F_cross, F_shared, C_cross,
+ * C_shared, sigma_c) must be NULL and sigma_mean needs LC_FISHER_MEAN (LC_ERR_INVALID, as unknown flags).  LC_FISHER_MEAN
+ * is the only flag: LC_FISHER_POSITIONS and LC_FISHER_PRIOR are LC_ERR_UNSUPPORTED (a batched object holds no prior, and
+ * without one the positions beside the shifts are singular), as is an object that is not batched (use
+ * lc_joint_fisher_shifts).  Every refusal happens before a launch, outputs untouched.  The zero-diagonal rule is per
+ * parameter as before; the pivot rule is per STAR: a pivot not above 1e-6 times its diagonal entry in any epoch of star g
+ * makes the C and sigma outputs of all of star g's epochs NaN and star_ok[g] = 0 (else 1; star_ok [G] may be NULL), and
+ * touches no other star; F stays as computed and the call returns LC_OK. */
+int lc_joint_groups_fisher_shifts(lc_joint *j, int flags, const lc_fisher_shifts_out *out, int32_t *star_ok);
 /* Multi-GPU epoch sharding: split one optimiser step around the caller's all-reduce of the shared block
  * [dL/dh (N*N) | dL/dc_x (M) | dL/dc_y (M) | sum_e (a - ref) (M) | sum_e (a - ref)^2 (M) | chi2 | n_epochs]
  * living in device memory.  The flux moments (flux-uniformity term, jnp.std over epochs in the reference:

@@ -231,6 +231,7 @@ SIGNATURES = {
     'lc_joint_fisher_flux_cov': (C.c_int, [vp, fp, fp, fp]),
     'lc_joint_fisher_positions': (C.c_int, [vp, C.c_int, C.POINTER(FisherPositionsOut)]),
     'lc_joint_fisher_shifts': (C.c_int, [vp, C.c_int, C.POINTER(FisherShiftsOut)]),
+    'lc_joint_groups_fisher_shifts': (C.c_int, [vp, C.c_int, C.POINTER(FisherShiftsOut), ip]),
     'lc_joint_step_local': (C.c_int, [vp]),
     'lc_joint_shared_buffer_dev': (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int)]),
     'lc_joint_step_update': (C.c_int, [vp, C.POINTER(AdabeliefCfg)]),

@@ -26,6 +26,12 @@
 // joint_fisher_shifts.h writes before the Gram kernel, and the solve kernels are instantiated at the local capacity 11 beside 9.
 // With shifts = 0 nothing of the existing call changes: same columns, values and bits.
 //
+// lc_joint_groups_fisher_shifts (a batch of stars, every star with its own positions and background) is the shifts mode with the
+// positions fixed and the epoch -> star map `group`: the template kernel reads the positions of the epoch's star, the shift
+// kernels its background, and the NaN rule holds per star - one verdict per star over that star's epochs (gstart), read by
+// the back-substitution of each of its epochs.  group[e] is read where it is used: the arithmetic of an epoch is that of the
+// one-object call, operation for operation.
+//
 // joint_fit.hip includes this file for the argument structures and the launchers; the kernels themselves are compiled by
 // joint_fisher_positions.hip (LC_FISHER_POSITIONS_KERNELS), a translation unit of their own: the set of kernels of
 // joint_fit.hip and their registers are pinned by tests/test_psf_budget_isa_cpu.py.
@@ -58,6 +64,9 @@ struct FisherTmplArgs {
   // frame, neither rotated nor weighted, in gsh [chunk][n n][2 M] for that kernel to add in source order
   int shifts = 0;
   float *gsh = nullptr;
+  // lc_joint_groups_fisher_shifts (batched star photometry): the star of every epoch [E]; source i of epoch e then sits at
+  // cx, cy [group[e] M + i].  Null: one object, one set of positions
+  const int *group = nullptr;
 };
 
 inline size_t fisher_tmpl_lds(int n, int ss) {
@@ -83,6 +92,10 @@ struct FisherArrowArgs {
   float *F_local, *F_cross, *F_shared, *C_local, *C_cross, *C_shared, *sigma_a, *sigma_mean, *sigma_c;
   int shifts = 0;      // the last two local parameters are dx_e, dy_e (local capacity kFpLocalShifts)
   float *sigma_dx = nullptr, *sigma_dy = nullptr;
+  // lc_joint_groups_fisher_shifts: `stars` stars, star g owns the epochs [gstart[g], gstart[g + 1]), group [E] is the star of every
+  // epoch.  The positions are fixed there (Sh = 0), and ok holds one verdict per star, [E + stars].  Null: one verdict for all
+  const int *group = nullptr, *gstart = nullptr;
+  int stars = 0;
 };
 
 // (joint_fisher_positions.hip) the template kernel on grid (bands, max(M, 1), epochs) with `lds` bytes; the Gram kernel on
@@ -121,8 +134,9 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_tmpl_kernel(FisherTmp
   const float inv_s2 = (float)inv_s2d, nrm = 0.3989422804014327f / kSigmaG;
   if (tid == 0) {
     const double al = (double)A.alpha[e] * 0.017453292519943295, ca = cos(al), sa = sin(al), c0 = (N - 1) * 0.5;
-    XY[0] = c0 + ss * (ca * (double)A.cx[i] - sa * (double)A.cy[i] + (double)A.dx[e]);
-    XY[1] = c0 + ss * (sa * (double)A.cx[i] + ca * (double)A.cy[i] + (double)A.dy[e]);
+    const int ci = (A.group ? A.group[e] * M : 0) + i;  // the epoch's own star's source
+    XY[0] = c0 + ss * (ca * (double)A.cx[ci] - sa * (double)A.cy[ci] + (double)A.dx[e]);
+    XY[1] = c0 + ss * (sa * (double)A.cx[ci] + ca * (double)A.cy[ci] + (double)A.dy[e]);
     XY[2] = ca;
     XY[3] = sa;
     WIN[0] = WIN[2] = N;
@@ -369,6 +383,14 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_shared_kernel(F
   __shared__ double Ld[kFpShared][kFpShared], Li[kFpShared][kFpShared];
   __shared__ int IDX[kFpShared], MM[2];
   const int tid = threadIdx.x, Lp = A.Lp, Sh = A.Sh, M = A.M;
+  if (A.gstart) {  // a batch: no shared block, and every star's verdict over its own epochs
+    for (int g = tid; g < A.stars; g += kFpThreads) {
+      int all = 1;
+      for (int e = A.gstart[g]; e < A.gstart[g + 1]; ++e) all &= A.ok[e];
+      A.ok[A.E + g] = all;
+    }
+    return;
+  }
   if (tid < Sh * Sh) {
     const int r = tid / Sh, c = tid % Sh;
     double f = 0.0, g = 0.0;
@@ -421,7 +443,7 @@ template <int KL>
 __global__ __launch_bounds__(kFpThreads) void joint_fisher_arrow_back_kernel(FisherArrowArgs A) {
   __shared__ double Cx[KL][kFpShared];
   const int e = blockIdx.x, tid = threadIdx.x, Lp = A.Lp, Sh = A.Sh, M = A.M;
-  const bool ok = A.ok[A.E] != 0;
+  const bool ok = A.ok[A.E + (A.group ? A.group[e] : 0)] != 0;  // the whole solve's verdict, in a batch the epoch's star's
   const float nan = __builtin_nanf("");
   const double *B = A.B + (size_t)e * KL * kFpShared, *Inv = A.Binv + (size_t)e * KL * KL;
   if (tid < Lp * Sh) {

@@ -15,6 +15,8 @@
 //      are wave-uniform (scalar loads; a row outside the PSF is replaced by a row of zeros).  float32, fixed order: q
 //      ascending within a row of A2, the rows' sums added in ascending y.  Then the mix and the two columns of the slab.
 // No atomics anywhere: two calls agree bit for bit.
+// A batch of stars (lc_joint_groups_fisher_shifts): the field kernel reads the background of the epoch's own star
+// (FisherShiftArgs::group); the column kernel never reads h itself, only the fields, and is the same for both.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,6 +35,10 @@ struct FisherShiftArgs {
   float *a2;          // [N] zeros, then [chunk][2][N + ss - 1][2 N]
   float *slab;        // [chunk][n n][32]
   int e0, M, n, ss, N, col;  // col: the column of dx_e (M + mean), dy_e follows
+  // lc_joint_groups_fisher_shifts with a background per star: the star of every epoch [E], h is [G][N][N] and epoch e reads
+  // h + group[e] N N.  Null: one background.  (A batch without a background passes h = null: its h is zero by construction,
+  // every background term an exact zero and x - 0 exact, so the columns are those of an object holding h = 0.)
+  const int *group = nullptr;
 };
 
 inline size_t fisher_shift_a2_floats(int chunk, int n, int ss) {
@@ -80,7 +86,7 @@ __global__ __launch_bounds__(kFpThreads) void joint_fisher_shift_field_kernel(Fi
       const int u = y + s, v = x + t;
       if (u < 0 || u >= N || v < 0 || v >= N) continue;
       float hx, hy;
-      fs_field(A.h, N, u, v, c0, ca, sa, sdx, sdy, hx, hy);
+      fs_field(A.h + (A.group ? (size_t)A.group[e] * N * N : 0), N, u, v, c0, ca, sa, sdx, sdy, hx, hy);  // its star's h
       sx += hx;
       sy += hy;
     }

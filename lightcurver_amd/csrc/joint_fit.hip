@@ -178,6 +178,8 @@ struct lc_joint {
   // lc_joint_fisher_shifts (allocated on first use): the sources' shift derivatives [fpos_chunk][n*n][2 M] and the box-summed
   // derivative fields of the background of one chunk (joint_fisher_shifts.h)
   float *fsh_gsh = nullptr, *fsh_a2 = nullptr;
+  // lc_joint_groups_fisher_shifts on a batch without a background (which has no gstart_dev): the stars' first epochs [G + 1]
+  int *fpos_gstart = nullptr;
   DevPool pool;  // everything dmalloc handed out; hist, ghist and phist are grown and freed on their own
 };
 
@@ -2686,9 +2688,11 @@ int lc_joint_fisher_flux_cov(lc_joint *j, float *fisher, float *cov, float *sigm
 
 // lc_joint_fisher_positions and lc_joint_fisher_shifts behind their argument checks: the slab of every chunk of epochs, its
 // Gram matrices, the arrowhead solve and the outputs.  `shifts`: dx_e, dy_e are local parameters too (out->sigma_dx, sigma_dy).
+// A batched object (lc_joint_groups_fisher_shifts: shifts, positions fixed): every epoch with its own star's positions and
+// background, one verdict per star -> star_ok [G] (may be null).
 static int fisher_arrowhead(lc_joint *j, const char *who, bool shifts, bool positions, bool mean, bool prior,
-                            const lc_fisher_shifts_out *out) {
-  const int E = j->E, M = j->M, n = j->n, nn = n * n;
+                            const lc_fisher_shifts_out *out, int32_t *star_ok = nullptr) {
+  const int E = j->E, M = j->M, n = j->n, nn = n * n, G = j->G;
   if (E == 0) return LC_OK;
   const int Lp = M + (mean ? 1 : 0) + (shifts ? 2 : 0), Sh = positions ? 2 * M : 0;
   const size_t lds = fisher_tmpl_lds(n, j->ss);
@@ -2707,10 +2711,21 @@ static int fisher_arrowhead(lc_joint *j, const char *who, bool shifts, bool posi
     int rc = dmalloc(j, &j->fpos_slab, (size_t)j->fpos_chunk * nn * kFpCols);
     if (!rc) rc = dmalloc(j, &j->fpos_work, (size_t)E * kPerEpoch + kFpShared * kFpShared);
     if (!rc) rc = dmalloc(j, &j->fpos_out, cap);
-    if (!rc) rc = dmalloc(j, &j->fpos_ok, (size_t)E + 1);
+    if (!rc) rc = dmalloc(j, &j->fpos_ok, (size_t)E + std::max(G, 1));
     if (rc) return rc;
   }
-  const float *h = j->par[LC_P_H];  // (no scan for zeros: an object that holds a background takes the background pass)
+  const int *gstart = j->gstart_dev;
+  if (G > 0 && !gstart) {
+    if (!j->fpos_gstart) {
+      int rc = dmalloc(j, &j->fpos_gstart, (size_t)G + 1);
+      if (!rc) rc = h2d(j, j->fpos_gstart, j->gstart.data(), j->gstart.size() * sizeof(int));
+      if (rc) return rc;
+    }
+    gstart = j->fpos_gstart;
+  }
+  // (no scan for zeros: an object that holds a background takes the background pass; a batch without one holds none - its
+  //  h is zero by construction, lc_joint_set_param refuses anything else - and its columns are those of h = 0 without the pass)
+  const float *h = (G > 0 && !j->bg) ? nullptr : j->par[LC_P_H];
   if (shifts && !j->fsh_gsh) {
     int rc = dmalloc(j, &j->fsh_gsh, (size_t)j->fpos_chunk * nn * 2 * M);
     // (zeroed by the allocation: the row of zeros at its start is never written)
@@ -2731,6 +2746,11 @@ static int fisher_arrowhead(lc_joint *j, const char *who, bool shifts, bool posi
   S.Lp = Lp;
   S.Sh = Sh;
   S.shifts = shifts ? 1 : 0;
+  if (G > 0) {
+    S.group = j->group_dev;
+    S.gstart = gstart;
+    S.stars = G;
+  }
   const size_t nFl = (size_t)E * Lp * Lp, nFx = (size_t)E * Lp * Sh, nFs = (size_t)Sh * Sh;
   S.F_local = j->fpos_out;
   S.F_cross = S.F_local + nFl;
@@ -2753,11 +2773,13 @@ static int fisher_arrowhead(lc_joint *j, const char *who, bool shifts, bool posi
       T.shifts = 1;
       T.gsh = j->fsh_gsh;
     }
+    if (G > 0) T.group = j->group_dev;
     launch_fisher_tmpl(T, bands, std::max(M, 1), e1 - e0, lds, q);
     LC_HIP(j->ctx, hipGetLastError());
     if (shifts) {
       FisherShiftArgs H{j->psf_dev, j->wgt, h, j->par[LC_P_DX], j->par[LC_P_DY], j->par[LC_P_ALPHA], j->fsh_gsh, j->fsh_a2,
                         j->fpos_slab, e0, M, n, j->ss, j->N, M + (mean ? 1 : 0)};
+      if (G > 0 && j->bg) H.group = j->group_dev;
       launch_fisher_shift_cols(H, e1 - e0, q);
       LC_HIP(j->ctx, hipGetLastError());
     }
@@ -2784,6 +2806,7 @@ static int fisher_arrowhead(lc_joint *j, const char *who, bool shifts, bool posi
   give(out->sigma_c, S.sigma_c, (size_t)Sh);
   give(out->sigma_dx, S.sigma_dx, shifts ? (size_t)E : 0);
   give(out->sigma_dy, S.sigma_dy, shifts ? (size_t)E : 0);
+  if (star_ok && G > 0) return d2h(j, star_ok, j->fpos_ok + E, (size_t)G * sizeof(int32_t));
   return LC_OK;
 }
 
@@ -2821,6 +2844,22 @@ int lc_joint_fisher_shifts(lc_joint *j, int flags, const lc_fisher_shifts_out *o
     LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_fisher_shifts: LC_FISHER_POSITIONS needs LC_FISHER_PRIOR - a common translation "
                                         "of the sources is a gauge of the epochs' shifts, and only the prior fixes it");
   return fisher_arrowhead(j, "lc_joint_fisher_shifts", true, positions, mean, prior, out);
+}
+
+int lc_joint_groups_fisher_shifts(lc_joint *j, int flags, const lc_fisher_shifts_out *out, int32_t *star_ok) {
+  if (!j || !out || (flags & ~(LC_FISHER_POSITIONS | LC_FISHER_MEAN | LC_FISHER_PRIOR))) return LC_ERR_INVALID;
+  LC_ENTER(j->ctx);
+  const std::string who = "lc_joint_groups_fisher_shifts";
+  const bool mean = flags & LC_FISHER_MEAN;
+  if (out->F_cross || out->F_shared || out->C_cross || out->C_shared || out->sigma_c)
+    LC_FAIL(j->ctx, LC_ERR_INVALID, who + ": no shared outputs - every star's positions stay fixed");
+  if (!mean && out->sigma_mean) LC_FAIL(j->ctx, LC_ERR_INVALID, who + ": sigma_mean needs LC_FISHER_MEAN");
+  if (flags & (LC_FISHER_POSITIONS | LC_FISHER_PRIOR))
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, who + ": LC_FISHER_POSITIONS / LC_FISHER_PRIOR - a batched star-photometry object holds no "
+                                        "prior, and without one the positions beside the shifts are singular (a gauge of the shifts)");
+  if (j->G == 0)
+    LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, who + ": not a batched star-photometry object (use lc_joint_fisher_shifts)");
+  return fisher_arrowhead(j, who.c_str(), true, false, mean, false, out, star_ok);
 }
 
 #ifdef LC_STAMPS

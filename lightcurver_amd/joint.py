@@ -382,7 +382,31 @@ class StarPhotometryBatch(JointFit):
         raise NotImplementedError('fisher_positions: the positions of a batched star photometry are per star')
 
     def fisher_shifts(self, positions=False, mean=False, prior=None):
-        raise NotImplementedError('fisher_shifts: not built for a batched star photometry')
+        raise NotImplementedError('fisher_shifts: not built for a batched star photometry (fisher_shifts_per_star: every '
+                                  "star's own call, positions fixed)")
+
+    def fisher_shifts_per_star(self, mean=False):
+        """Every star's ``JointFit.fisher_shifts(mean=mean)`` in one call (lc_joint_groups_fisher_shifts): theta = (a, dx, dy[,
+        mean]) of all stars, each star's c_x, c_y fixed (the gauge of its shifts), alpha and h too.  The information is block
+        diagonal over the epochs; returns the concatenated arrays, in the order of the batch (``split`` cuts the per-epoch ones
+        by star):
+          F_local, C_local (E, Lp, Lp)   a_e, mean_e, dx_e, dy_e (Lp = M + 2, with ``mean`` M + 3);
+          sigma_a (E * M,), sigma_mean (E,) (empty without ``mean``), sigma_dx, sigma_dy (E,);   star_ok (G,) bool
+        Star g's part is bit for bit what a JointFit on that star's stacks and parameters returns (for a batch without
+        backgrounds: one holding h = 0).  A parameter with a zero diagonal entry has sigma = inf and zero rows and columns of C;
+        a numerically singular block in one epoch of a star makes that star's C and sigma NaN and ``star_ok[g]`` False, and
+        leaves every other star as it is."""
+        E, M = self.E, self.M
+        Lp = M + (1 if mean else 0) + 2
+        shapes = {'F_local': (E, Lp, Lp), 'C_local': (E, Lp, Lp), 'sigma_a': (E * M,), 'sigma_mean': (E if mean else 0,),
+                  'sigma_dx': (E,), 'sigma_dy': (E,)}
+        res = {k: np.zeros(shapes[k], np.float32) for k in _lib.FISHER_SHIFTS_FIELDS if k in shapes}
+        out = _lib.FisherShiftsOut(**{k: ptr(v) for k, v in res.items() if v.size})
+        ok = np.zeros(self.G, np.int32)
+        self._chk(self._l.lc_joint_groups_fisher_shifts(self.h, _lib.FISHER_MEAN if mean else 0, C.byref(out),
+                                                        ok.ctypes.data_as(_lib.ip)), 'groups_fisher_shifts')
+        res['star_ok'] = ok != 0
+        return res
 
     def split(self, flat, name):
         """The concatenated block ``name`` as a list of per-star arrays."""

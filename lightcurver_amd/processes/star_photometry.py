@@ -110,7 +110,7 @@ def do_one_star_forward_modelling(data, noisemap, psf, subsampling_factor, n_ite
 
 
 def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uniform_background_per_epoch=False,
-                                    starlet_global_background=False):
+                                    starlet_global_background=False, marginalize_shifts=False):
     """The reference's loop over its reference stars (star_photometry.py:257-326: ``do_one_star_forward_modelling`` once per
     star, each a 2000-iteration fit) as ONE batched device fit (``lightcurver_amd.joint.StarPhotometryBatch``,
     lc_joint_create_groups): every AdaBelief iteration advances all stars with one kernel pair instead of one pair per star.
@@ -134,7 +134,17 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
 
     Returns one dictionary per star with ALL keys of ``do_one_star_forward_modelling`` (``deconvolved_image``: the scene of the
     star's first epoch, ``starlet_background``: zeros when no background is fitted - what the reference's caller reads at
-    star_photometry.py:139-150); each star's numbers are bit for bit those of its own one-star fit."""
+    star_photometry.py:139-150); each star's numbers are bit for bit those of its own one-star fit.
+
+    ``marginalize_shifts``: every star's dictionary also gets ``fluxes_uncertainties_marginal`` (E_g,), the 1-sigma of the
+    fluxes marginal over the epochs' translations dx, dy the fit frees (and over ``mean`` where
+    ``uniform_background_per_epoch`` frees it), the star's position fixed: ``scale * sqrt(C_local[e, 0, 0])`` of
+    ``StarPhotometryBatch.fisher_shifts_per_star`` (lc_joint_groups_fisher_shifts, all stars in one call) at the batch's final
+    parameters.  One difference from the one-star function: that one polishes the fluxes with 10 L-BFGS-B iterations
+    before its Fisher call and the batch does not (lc_joint_run_lbfgs is not available on a batch); with the shifts free
+    the information depends on ``a``, so the two agree closely after a converged fit, not bit for bit.  A star with a
+    numerically singular epoch has NaN there, and no other star is touched.  Without the switch the dictionaries are
+    unchanged and have no such key."""
     from ..joint import StarPhotometryBatch, EmbeddedJointFit, joint_fit_size, background_batch_supported
     from ..starred.deconvolution.deconvolution import nest_kwargs
     ss = int(subsampling_factor)
@@ -153,7 +163,8 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
     pad = (n_fit - n_user) // 2
     if starlet_global_background and not background_batch_supported(n_fit, ss):
         return [do_one_star_forward_modelling(d, nm, p, ss, n_iter=n_iter, uniform_background_per_epoch=uniform_background_per_epoch,
-                                              starlet_global_background=True) for d, nm, p in stacks]
+                                              starlet_global_background=True, marginalize_shifts=marginalize_shifts)
+                for d, nm, p in stacks]
 
     def embed(a, fill, f=1):
         if pad == 0:
@@ -195,6 +206,8 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
         model, _ = batch.model()
         model = model[:, pad:pad + n_user, pad:pad + n_user]
         sigma_a = batch.fisher_flux_sigma()
+        # (the shifts free, and mean where the fit had it free, every star's position fixed: C_local [E][Lp][Lp], a_e first)
+        marginal = batch.fisher_shifts_per_star(mean=bool(uniform_background_per_epoch))['C_local'] if marginalize_shifts else None
         decon = [batch.deconvolved(int(batch.starts[g])) for g in range(G)]
         scenes = [s[P:P + Nu, P:P + Nu] for s, _ in decon]
         backgrounds = [b[P:P + Nu, P:P + Nu] for _, b in decon]
@@ -222,6 +235,8 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
             'deconvolved_image': scale * np.ascontiguousarray(scenes[g]),
             'starlet_background': scale * (np.ascontiguousarray(backgrounds[g]) if bg else np.zeros((n_user * ss, n_user * ss), np.float32)),
         })
+        if marginalize_shifts:
+            out[-1]['fluxes_uncertainties_marginal'] = scale * np.sqrt(np.array(marginal[e0:e1, 0, 0], dtype=np.float64))
     return out
 
 

@@ -552,6 +552,18 @@ int lc_joint_supported(int n, int ss);
 int lc_joint_set_debug_global(int on);
 int lc_joint_create(lc_ctx *ctx, int E, int M, int n, int ss, const float *data, const float *sigma2,
                     const float *psf, lc_joint **out);
+/* ... with PSF stamps of their own side: psf [E][psf_side][psf_side], any psf_side >= 1 (the reference fits its narrow
+ * PSFs at stamp_size_stars and cuts the ROI at stamp_size_ROI, two independent settings: 24 and 32 by default, so
+ * 48 x 48 stamps beside a 64 x 64 grid).  A stamp is placed on the N x N grid, N = n * ss, with the zero lags of the
+ * 'same' convolution coinciding: tap (a, b) goes to (a + c_N - c_P, b + c_N - c_P), c_S = (S - 1) / 2; taps outside
+ * [0, N) are dropped and nothing is renormalised.  For psf_side <= N that is the same linear operator as convolving with
+ * the stamp; for psf_side > N the N x N window is all the fit carries (the dropped wings are a declared approximation,
+ * DESIGN.md section 7).  lc_joint_create is this call with psf_side = n * ss, bit for bit.  LC_ERR_INVALID for
+ * psf_side < 1, LC_ERR_UNSUPPORTED for E * psf_side^2 >= 2^31 or, with psf_side != n * ss, E > 65535; refused before
+ * anything is allocated, *out untouched.  The grouped creators below keep psf [sum E_g][N][N]: in the reference a star's
+ * PSF and its stamp are both stamp_size_stars. */
+int lc_joint_create_psf(lc_ctx *ctx, int E, int M, int n, int ss, int psf_side, const float *data, const float *sigma2,
+                        const float *psf /* [E][psf_side][psf_side] */, lc_joint **out);
 void lc_joint_destroy(lc_joint *j);
 int lc_joint_set_param(lc_joint *j, int which, const float *values, int count);
 int lc_joint_get_param(lc_joint *j, int which, float *values, int count);

@@ -204,6 +204,7 @@ SIGNATURES = {
     'lc_joint_groups_background_supported': (C.c_int, [C.c_int, C.c_int]),
     'lc_joint_set_debug_global': (C.c_int, [C.c_int]),
     'lc_joint_create': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]),
+    'lc_joint_create_psf': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]),
     'lc_joint_create_groups': (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]),
     'lc_joint_create_groups_background': (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(vp)]),
     'lc_joint_get_group_loss_history': (C.c_int, [vp, fp, C.c_int]),

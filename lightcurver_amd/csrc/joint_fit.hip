@@ -16,6 +16,7 @@
 #include "joint_reg_fused.h"
 #include "joint_ps.h"
 #include "joint_noise.h"
+#include "joint_psf_place.h"
 #include "joint_lbfgs.h"
 #include "joint_fisher.h"
 #include "joint_fisher_positions.h"
@@ -164,7 +165,8 @@ struct lc_joint {
   // return_param_history: device-resident [phist_cap][phist_P] rows of the free blocks, one per AdaBelief update
   float *phist = nullptr;
   int phist_cap = 0, phist_P = 0, phist_rows = 0, phist_off[LC_P_COUNT] = {};
-  std::vector<float> h_sigma2, h_psf;  // host copies for the one-time noise propagation
+  std::vector<float> h_sigma2, h_psf;  // host copies for the one-time noise propagation (h_psf: the stamps at their own side)
+  int psf_side = 0;                    // side P of the PSF stamps handed in (joint_psf_place.h puts them on the N x N grid)
   // lc_joint_fisher_flux_cov (allocated on first use): the template slab [fcov_chunk][M][n*n] of one chunk of epochs, and
   // F, C [E][M][M], sigma [E][M] one after the other
   float *tmpl = nullptr, *fcov = nullptr;
@@ -198,6 +200,21 @@ int h2d(lc_joint *j, void *dst, const void *src, size_t bytes) {
 int d2h(lc_joint *j, void *dst, const void *src, size_t bytes) {
   LC_HIP(j->ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, j->ctx->stream));
   LC_HIP(j->ctx, hipStreamSynchronize(j->ctx->stream));
+  return LC_OK;
+}
+
+// psf_dev [E][N][N] from stamps [E][P][P] of another side (joint_psf_place.h): the stamps go up into a buffer of this call,
+// one launch places them, and the synchronise that the upload of a full-size stack ends with (h2d) stands behind both
+int place_psf_stamps(lc_joint *j, const float *psf, int P) {
+  lc_ctx *ctx = j->ctx;
+  const size_t count = (size_t)j->E * P * P;
+  DevPool stamps;
+  float *stamp_dev = nullptr;
+  LC_HIP(ctx, stamps.alloc(count, &stamp_dev));
+  LC_HIP(ctx, hipMemcpyAsync(stamp_dev, psf, count * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  launch_psf_place(j->E, P, j->N, stamp_dev, j->psf_dev, ctx->stream);
+  LC_HIP(ctx, hipGetLastError());
+  LC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LC_OK;
 }
 
@@ -1123,13 +1140,17 @@ int lc_joint_set_debug_global(int on) {
   return LC_OK;
 }
 
-static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const float *data, const float *sigma2,
+static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, int psf_side, const float *data, const float *sigma2,
                              const float *psf, int G, const int32_t *epochs_per_group, lc_joint **out, bool background = false);
 static int create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss, const float *data,
                          const float *sigma2, const float *psf, lc_joint **out, bool background);
 int lc_joint_create(lc_ctx *ctx, int E, int M, int n, int ss, const float *data, const float *sigma2,
                     const float *psf, lc_joint **out) {
-  return joint_create_impl(ctx, E, M, n, ss, data, sigma2, psf, 0, nullptr, out);
+  return joint_create_impl(ctx, E, M, n, ss, n * ss, data, sigma2, psf, 0, nullptr, out);
+}
+int lc_joint_create_psf(lc_ctx *ctx, int E, int M, int n, int ss, int psf_side, const float *data, const float *sigma2,
+                        const float *psf, lc_joint **out) {
+  return joint_create_impl(ctx, E, M, n, ss, psf_side, data, sigma2, psf, 0, nullptr, out);
 }
 int lc_joint_create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, int M, int n, int ss, const float *data,
                            const float *sigma2, const float *psf, lc_joint **out) {
@@ -1157,14 +1178,19 @@ static int create_groups(lc_ctx *ctx, int G, const int32_t *epochs_per_group, in
     if (!lc_joint_groups_background_supported(n, ss))
       LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_joint_create_groups_background: stamp sizes with a single-workgroup update only (n = 16, 24, 32 at ss = 2, n = 16 at ss = 1)");
   }
-  return joint_create_impl(ctx, (int)E, M, n, ss, data, sigma2, psf, G, epochs_per_group, out, background);
+  return joint_create_impl(ctx, (int)E, M, n, ss, n * ss, data, sigma2, psf, G, epochs_per_group, out, background);
 }
-static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const float *data, const float *sigma2,
+static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, int psf_side, const float *data, const float *sigma2,
                              const float *psf, int G, const int32_t *epochs_per_group, lc_joint **out, bool background) {
   if (!ctx || !out || !data || !sigma2 || !psf || E <= 0 || M < 0) {
     if (ctx) ctx->err = "lc_joint_create: invalid argument";
     return LC_ERR_INVALID;
   }
+  if (psf_side < 1) LC_FAIL(ctx, LC_ERR_INVALID, "lc_joint_create_psf: psf_side must be at least 1");
+  if ((long long)E * psf_side * psf_side >= (1LL << 31))
+    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_joint_create_psf: E * psf_side^2 must stay below 2^31");
+  if (psf_side != n * ss && E > 65535)  // (the placement's grid has one row of blocks per epoch)
+    LC_FAIL(ctx, LC_ERR_UNSUPPORTED, "lc_joint_create_psf: at most 65535 epochs with PSF stamps of another side than the grid");
   // grouped objects run the point-source-only kernel and nothing else: no spectra, no background work space (except the
   // per-star background form, which has them all: bgG stars' worth of the per-star blocks)
   const bool lean = G > 0 && !background;
@@ -1317,9 +1343,16 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
   }
   {
     // PSF spectra: FFT2 of the zero-padded narrow PSF, stored transposed and pre-divided by L^2
-    if (!lean) j->h_psf.assign(psf, psf + E * NN);
+    const int P = psf_side;
+    const size_t PP = (size_t)P * P;
+    j->psf_side = P;
+    if (!lean) j->h_psf.assign(psf, psf + E * PP);
     TRY(dmalloc(j, &j->psf_dev, (size_t)E * NN));
-    TRY(h2d(j, j->psf_dev, psf, (size_t)E * NN * sizeof(float)));
+    if (P == N) {  // the placement is the identity (the grouped creators, whose E may exceed a launch's grid, are always here)
+      TRY(h2d(j, j->psf_dev, psf, (size_t)E * NN * sizeof(float)));
+    } else {
+      TRY(place_psf_stamps(j, psf, P));
+    }
     if (lean) {
       ps_fn pk = nullptr;
       int plds = 0;
@@ -1344,7 +1377,10 @@ static int joint_create_impl(lc_ctx *ctx, int E, int M, int n, int ss, const flo
           for (int e = t; e < E; e += T) {
             std::fill(a.begin(), a.end(), cd(0, 0));
             for (int r = 0; r < N; ++r)
-              for (int c = 0; c < N; ++c) a[(size_t)r * L + c] = psf[(size_t)e * NN + (size_t)r * N + c];
+              for (int c = 0; c < N; ++c) {
+                const int src = psf_place_source(P, N, r * N + c);
+                a[(size_t)r * L + c] = src >= 0 ? psf[(size_t)e * PP + src] : 0.f;
+              }
             host_fft2d(a, L, 0, N, false);
             float2 *se = st.data() + (size_t)e * KH * L;
             for (int k = 0; k < KH; ++k)
@@ -1623,7 +1659,7 @@ int lc_joint_propagate_noise(lc_joint *j, float *W_out) {
   if (!j) return LC_ERR_INVALID;
   LC_ENTER(j->ctx);
   if (j->G > 0 && !j->bg) LC_FAIL(j->ctx, LC_ERR_UNSUPPORTED, "lc_joint_propagate_noise: not available on a batched star-photometry object");
-  const int N = j->N, n = j->n, ss = j->ss, E = j->E, c = (N - 1) / 2;
+  const int N = j->N, n = j->n, ss = j->ss, E = j->E, c = (N - 1) / 2, P = j->psf_side;
   const size_t NN = (size_t)N * N, nn = (size_t)n * n;
   if (!std::getenv("LCMI_NOISE_HOST") || j->bg) {
     int rc = propagate_noise_device(j);
@@ -1648,14 +1684,15 @@ int lc_joint_propagate_noise(lc_joint *j, float *W_out) {
       std::vector<double> r(NN);
       const int b0 = ss * (n / 2);
       for (int e = t; e < E; e += T) {
-        const float *s = &j->h_psf[(size_t)e * NN];
+        const float *s = &j->h_psf[(size_t)e * P * P];
         for (int up = 0; up < N; ++up)
           for (int vp = 0; vp < N; ++vp) {
             double acc = 0;
             for (int du = 0; du < ss; ++du)
               for (int dv = 0; dv < ss; ++dv) {
                 const int a = b0 + du - up + c, b = b0 + dv - vp + c;
-                if (a >= 0 && a < N && b >= 0 && b < N) acc += s[(size_t)a * N + b];
+                const int src = (a >= 0 && a < N && b >= 0 && b < N) ? psf_place_source(P, N, a * N + b) : -1;
+                if (src >= 0) acc += s[src];
               }
             r[(size_t)up * N + vp] = acc;
           }

@@ -165,7 +165,8 @@ ROI_FILE_KEYS = ('frame_id', 'data', 'noisemap', 'psf', 'seeing', 'sky_level_ele
 def read_roi_file(roi_file):
     """The calibrated ROI stack written by roi_file_preparation.py:215-229 as the arguments of
     ``processes.roi_modelling.model_roi_cutouts``: everything in ROI_FILE_KEYS, plus ``subsampling`` (the single value
-    the reference takes with np.unique at roi_modelling.py:166-170)."""
+    the reference takes with np.unique at roi_modelling.py:166-170) and ``psf_side`` (the PSF stack is (E, P, P) with a side of
+    its own, any P: joint.place_psf)."""
     with open_regions(roi_file) as root:
         missing = [k for k in ('data', 'noisemap', 'psf', 'subsampling_factor') if k not in root.keys()]
         if missing:
@@ -176,7 +177,9 @@ def read_roi_file(roi_file):
         raise ValueError(f'all epochs must share one subsampling factor, found {ss}')
     out['subsampling'] = int(ss[0])
     E, n, _ = out['data'].shape
-    N = out['subsampling'] * n
-    if out['noisemap'].shape != (E, n, n) or out['psf'].shape != (E, N, N):
+    psf = out['psf']
+    # (the PSF stamps have their own side: roi_file_preparation.py writes them at stamp_size_stars, the data at stamp_size_ROI)
+    if out['noisemap'].shape != (E, n, n) or psf.ndim != 3 or psf.shape[0] != E or psf.shape[1] != psf.shape[2]:
         raise ValueError('data / noisemap / psf shapes are inconsistent')
+    out['psf_side'] = int(psf.shape[1])
     return out

@@ -1,6 +1,7 @@
 """Thin Python object over the lc_joint_* entry points: the device-resident joint multi-epoch
 forward model (STARRED ``Deconv`` + ``Loss`` + optimiser state)."""
 import ctypes as C
+import warnings
 
 import numpy as np
 
@@ -8,8 +9,44 @@ from . import _lib
 from ._lib import PARAM_INDEX, P_COUNT, f32, ptr
 
 
+def place_psf(psf, N):
+    """PSF stamps (E, P, P) on the (E, N, N) grid of a joint fit, the zero lags of the 'same' convolution coinciding
+    (csrc/joint_psf_place.h is the library's form): tap (a, b) goes to (a + c_N - c_P, b + c_N - c_P),
+    c_S = (S - 1) // 2, taps outside the grid are dropped, nothing is renormalised.  For P <= N convolving with the result is
+    convolving with the stamp; for P > N it is the stamp's central N x N window.  A new array of the stamps' dtype."""
+    psf = np.asarray(psf)
+    E, P, _ = psf.shape
+    N = int(N)
+    off = (N - 1) // 2 - (P - 1) // 2
+    lo, hi = max(off, 0), min(off + P, N)
+    out = np.zeros((E, N, N), psf.dtype)
+    out[:, lo:hi, lo:hi] = psf[:, lo - off:hi - off, lo - off:hi - off]
+    return out
+
+
+def psf_flux_outside(psf, N):
+    """Largest fraction over the epochs of a PSF stamp's flux that lies outside the N x N window ``place_psf`` keeps
+    (0.0 for stamps no larger than the grid)."""
+    psf = np.asarray(psf, dtype=np.float64)
+    if psf.shape[-1] <= N:
+        return 0.0
+    return float(np.max(1.0 - place_psf(psf, N).sum(axis=(1, 2)) / psf.sum(axis=(1, 2))))
+
+
+def _psf_stack(psf, E):
+    if psf.ndim != 3 or psf.shape[0] != E or psf.shape[1] != psf.shape[2] or psf.shape[1] < 1:
+        raise ValueError(f'psf must be ({E}, P, P) with P >= 1, got {psf.shape}')
+    return psf.shape[1]
+
+
+def _warn_windowed(P, N, lost):
+    warnings.warn(f'PSF stamps of side {P} are wider than the {N} x {N} grid of the fit: the central window is used, '
+                  f'at most {lost:.8e} of a stamp\'s flux lies outside it', UserWarning, stacklevel=3)
+
+
 class JointFit:
-    """data, sigma2: (E, n, n); psf: (E, N, N) narrow PSFs, N = ss * n; M point sources."""
+    """data, sigma2: (E, n, n); psf: (E, P, P) narrow PSFs of any side P >= 1, placed on the N x N grid of the fit,
+    N = ss * n, by the rule of ``place_psf`` (``psf_side`` keeps P; P > N is windowed and warns); M point sources."""
 
     def __init__(self, data, sigma2, psf, ss, M, ctx=None):
         data, sigma2, psf = f32(data), f32(sigma2), f32(psf)
@@ -19,16 +56,17 @@ class JointFit:
         self.ss = int(ss)
         self.N = self.n * self.ss
         self.M = int(M)
-        if psf.shape != (self.E, self.N, self.N):
-            raise ValueError(f'psf must be ({self.E}, {self.N}, {self.N}), got {psf.shape}')
+        self.psf_side = _psf_stack(psf, self.E)
+        if self.psf_side > self.N:
+            _warn_windowed(self.psf_side, self.N, psf_flux_outside(psf, self.N))
         self.J = int(np.log2(self.N))
         self.ctx = ctx or _lib.default_context()
         self._l = _lib.lib()
         if not self._l.lc_joint_supported(self.n, self.ss):
             raise _lib.LcError(f'no joint-fit kernel for stamp size n={self.n}, subsampling {self.ss}')
         h = C.c_void_p()
-        self.ctx.check(self._l.lc_joint_create(self.ctx.h, self.E, self.M, self.n, self.ss, ptr(data), ptr(sigma2),
-                                               ptr(psf), C.byref(h)), 'lc_joint_create')
+        self.ctx.check(self._l.lc_joint_create_psf(self.ctx.h, self.E, self.M, self.n, self.ss, self.psf_side, ptr(data),
+                                                   ptr(sigma2), ptr(psf), C.byref(h)), 'lc_joint_create_psf')
         self.h = h
         self.sizes = {'a': self.E * self.M, 'c_x': self.M, 'c_y': self.M, 'dx': self.E, 'dy': self.E,
                       'alpha': self.E, 'h': self.N * self.N, 'mean': self.E}
@@ -464,7 +502,8 @@ def ring_at_median_variance(var, sigma2, pad):
 class EmbeddedJointFit(JointFit):
     """The reference's ``stamp_size_ROI`` / ``stamp_size_stars`` are free integers (config.yaml:205-206); the epoch kernels exist
     for n = 8 k <= 64 and 128.  An even n in between is fitted EMBEDDED in the next of those, as a declared fall-back: the
-    stamps in the centre of the larger frame, no weight on the ring (variance 1e20), the narrow PSFs zero-padded, the
+    stamps in the centre of the larger frame, no weight on the ring (variance 1e20), the narrow PSFs (any side, windowed to the
+    caller's N = ss n by ``place_psf``) placed on the larger grid, the
     background h fitted on the larger grid.  Towards the caller everything keeps the caller's size: ``h`` goes in padded
     with zeros and comes out cropped (values, gradients, bounds, parameter history), models and deconvolved images are
     cropped.  Inside the caller's window the model is the native-size one (the convolution window is alias-free in both)
@@ -485,19 +524,21 @@ class EmbeddedJointFit(JointFit):
         ss = int(ss)
         if (n_fit - n) % 2 or n_fit <= n:
             raise ValueError('embedding needs a larger size of the same parity')
-        if psf.shape != (E, n * ss, n * ss):
-            raise ValueError(f'psf must be ({E}, {n * ss}, {n * ss}), got {psf.shape}')
+        psf_side = _psf_stack(psf, E)
+        if psf_side > n * ss:
+            _warn_windowed(psf_side, n * ss, psf_flux_outside(psf, n * ss))
         self.pad, self.n_user, self.N_user = (n_fit - n) // 2, n, n * ss
-        p, P = self.pad, self.pad * ss
+        p = self.pad
         big = np.zeros((E, n_fit, n_fit), np.float32)
         big[:, p:p + n, p:p + n] = data
         var = np.full((E, n_fit, n_fit), self.RING_VARIANCE, np.float32)
         var[:, p:p + n, p:p + n] = sigma2
-        self._psf_fit = np.zeros((E, n_fit * ss, n_fit * ss), np.float32)
-        self._psf_fit[:, P:P + n * ss, P:P + n * ss] = psf
+        # (the caller's window first, whatever the fitted size: a result does not depend on which sizes have kernels)
+        self._psf_fit = place_psf(place_psf(psf, n * ss), n_fit * ss)
         # (for the noise propagation: the ring at each epoch's median variance)
         self._var_w = ring_at_median_variance(var, sigma2, p)
         super().__init__(big, var, self._psf_fit, ss, M, ctx)
+        self.psf_side = psf_side
         self._dev_dims = (self.n, self.N, dict(self.sizes))
         self._user_dims = (n, n * ss, dict(self.sizes, h=(n * ss) ** 2))
         self.n, self.N, self.sizes = self._user_dims

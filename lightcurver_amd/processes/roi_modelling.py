@@ -64,7 +64,7 @@ def model_roi_cutouts(data, noisemap, psf, subsampling_factor, xs_pixels, ys_pix
                       starting_background=None, further_optimize_background=True, regularization=None,
                       roi_deconv_translations_iters=300, roi_deconv_all_iters=2000, rescale=True,
                       marginalize_positions=False, aperture_method='center', marginalize_shifts=False):
-    """data, noisemap (E, n, n); psf (E, N, N); xs_pixels, ys_pixels: point-source positions in pixels of
+    """data, noisemap (E, n, n); psf (E, P, P), any side P (joint.place_psf); xs_pixels, ys_pixels: point-source positions in pixels of
     the first epoch (0-based, as astropy's world_to_pixel returns them).  ``aperture_method``: how the starting fluxes are
     summed where ``initial_a`` is not given (``initial_point_source_fluxes``: 'center', or 'exact' as the reference).
 
@@ -177,7 +177,7 @@ def model_roi_cutouts_sharded(data, noisemap, psf, subsampling_factor, xs_pixels
                               roi_deconv_all_iters=2000, further_optimize_background=True, ctx=None,
                               return_flux_covariance=False, marginalize_positions=False, marginalize_shifts=False):
     """The two-stage fit of ``model_roi_cutouts`` with the epochs spread over the ranks of a torch.distributed group (one
-    process per GPU): every rank passes ITS epochs - data, noisemap (E_local, n, n), psf (E_local, N, N) - and the same
+    process per GPU): every rank passes ITS epochs - data, noisemap (E_local, n, n), psf (E_local, P, P) - and the same
     ``initial_a`` (M fluxes) and ``scale`` (nanmax of the data of ALL epochs: ``global_scale``).  The reference has no
     counterpart (it keeps all epochs on one device, roi_modelling.py:154-160,213); this is what BASELINE configs[4] (1000
     epochs of 128 x 128 over eight GPUs) runs.

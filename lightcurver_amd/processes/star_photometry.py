@@ -40,7 +40,8 @@ def _border_level(stack):
 def do_one_star_forward_modelling(data, noisemap, psf, subsampling_factor, n_iter=2000,
                                   uniform_background_per_epoch=False, starlet_global_background=True,
                                   marginalize_shifts=False):
-    """data, noisemap: (E, n, n) (rescaled IN PLACE by nanmax(data)); psf: (E, N, N) narrow PSFs.
+    """data, noisemap: (E, n, n) (rescaled IN PLACE by nanmax(data)); psf: (E, P, P) narrow PSFs, any side P
+    (joint.place_psf).
 
     Returns dict: scale, kwargs_final, fluxes, fluxes_uncertainties, chi2, chi2_per_frame, loss_curve,
     residuals, deconvolved_image, starlet_background.  ``marginalize_shifts``: also ``fluxes_uncertainties_marginal`` (E,),

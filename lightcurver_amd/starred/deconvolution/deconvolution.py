@@ -100,7 +100,7 @@ def _fingerprint(a):
 def setup_model(data, sigma_2, s, xs, ys, subsampling_factor, initial_a, ctx=None):
     """Build the model and the initial / bound / fixed kwargs, as STARRED's ``setup_model`` does.
 
-    data, sigma_2: (E, n, n); s: (E, N, N) narrow PSFs; xs, ys: M initial positions (data pixels,
+    data, sigma_2: (E, n, n); s: (E, P, P) narrow PSFs of any side P (joint.place_psf); xs, ys: M initial positions (data pixels,
     origin at the stamp centre); initial_a: E*M fluxes, epoch-major.
     """
     data = np.asarray(data)

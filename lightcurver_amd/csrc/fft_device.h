@@ -219,14 +219,18 @@ __device__ __forceinline__ void dit_stage_inv(float2 (&x)[L / LPF], int j, const
 // Transforms over LPF = 16 lanes (four per wave) or 32 lanes (two per wave; the longest grids, whose 24 registers per
 // lane at LPF = 16 would not leave room for anything else): transform index of a lane / lane of an index, and the bit
 // reversal of the block layout
+// ... or over LPF = 8 lanes (eight per wave: grids whose side is a multiple of 8 and not of 16 - N = 24, 40, 56): the three
+// exchanges that stay inside half a DPP row (lane ^ 1, lane ^ 2, lane ^ 7), the same lane order, no span-8 stage
 template <int LPF>
 __device__ __forceinline__ int fft_index_n(int l) {
-  if constexpr (LPF == 16) return fft_index(l);
+  static_assert(LPF == 8 || LPF == 16 || LPF == 32, "lanes per transform");
+  if constexpr (LPF <= 16) return fft_index(l);
   else return fft_index(l & 15) | (l & 16);
 }
 template <int LPF>
 __device__ __forceinline__ int bitrev_n(int x) {
-  if constexpr (LPF == 16) return bitrev4(x);
+  if constexpr (LPF == 8) return ((x & 1) << 2) | (x & 2) | ((x & 4) >> 2);
+  else if constexpr (LPF == 16) return bitrev4(x);
   else return (bitrev4(x & 15) << 1) | ((x >> 4) & 1);
 }
 // tw[m] = exp(-2 pi i m / L), m < L (LDS)
@@ -242,7 +246,7 @@ __device__ __forceinline__ void group_fft_fwd(float2 (&x)[L / LPF], int j, const
 #pragma unroll
   for (int k2 = 1; k2 < N2; ++k2) x[k2] = cmul(x[k2], tw[j * k2]);
   if constexpr (LPF == 32) dif_stage<L, 16, LPF>(x, j, tw);
-  dif_stage<L, 8, LPF>(x, j, tw);
+  if constexpr (LPF >= 16) dif_stage<L, 8, LPF>(x, j, tw);
   dif_stage<L, 4, LPF>(x, j, tw);
   dif_stage<L, 2, LPF>(x, j, tw);
   dif_stage<L, 1, LPF, ODDNEG>(x, j, tw);
@@ -254,7 +258,7 @@ __device__ __forceinline__ void group_fft_inv(float2 (&x)[L / LPF], int j, const
   dit_stage_inv<L, 1, LPF, ODDNEG>(x, j, tw);
   dit_stage_inv<L, 2, LPF>(x, j, tw);
   dit_stage_inv<L, 4, LPF>(x, j, tw);
-  dit_stage_inv<L, 8, LPF>(x, j, tw);
+  if constexpr (LPF >= 16) dit_stage_inv<L, 8, LPF>(x, j, tw);
   if constexpr (LPF == 32) dit_stage_inv<L, 16, LPF>(x, j, tw);
 #pragma unroll
   for (int k2 = 1; k2 < N2; ++k2) {

@@ -15,6 +15,7 @@
 #include "joint_reg_mfma.h"
 #include "joint_reg_fused.h"
 #include "joint_ps.h"
+#include "joint_variants.h"
 #include "joint_noise.h"
 #include "joint_psf_place.h"
 #include "joint_lbfgs.h"
@@ -30,35 +31,7 @@ static_assert(kFpMaxSources == kMaxSources && kFpPivot == kFisherPivot, "joint_f
 constexpr int kMaxParts = 16;  // workgroups per epoch of the phased launches
 constexpr int kRegChainCUs = 64;  // CUs the cluster form of the epoch kernel leaves to the regulariser chain beside it (cluster_parts)
 constexpr int kRegsStride = 4 + 3 * kMaxSources + 4;  // floats of lc_joint::regs (per star of a batch with backgrounds)
-typedef void (*epoch_fn)(JointArgs);
-typedef void (*update_fn)(JointUpdArgs);
-struct JointVariant {
-  int n, ss, L;
-  epoch_fn ek;
-  int e_lds, e_thr;
-  update_fn uk;  // null: regulariser + update run as global-memory kernels (joint_gm.h)
-  int u_thr, u_lds;
-  bool gspec;
-  epoch_fn ek_aux;  // plain convolution / spectrum modes of the same pipeline (noise propagation)
-  epoch_fn ek_tile = nullptr;  // global-spectrum kernels: the variant whose column passes go through an LDS tile
-  int e_lds_tile = 0;
-  // global-spectrum kernels: one phase (A, B, C, B', C', D) per launch on a grid (E, parts); [1] / [3] also in the tile build
-  epoch_fn ek_phase[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  epoch_fn ek_phase_tile[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int e_lds_lite = 0, e_lds_lite_tile = 0;  // LDS of the column phases and of phase D (JointCfg::LDS_LITE)
-  int lpf = 16;                             // lanes per transform (JointCfg::LPF)
-  // cluster form (joint_kernels.h, PHASE = 7): several workgroups per epoch in ONE launch, spectrum in the global scratch;
-  // a build of its own beside an LDS-spectrum kernel (same N, SS, L: same spectra)
-  epoch_fn ek_cluster = nullptr;
-  int cl_lds = 0, cl_thr = 0, cl_lpf = 16;
-  // batched star photometry with a background grid per star (lc_joint_create_groups_background): the epoch kernel that reads
-  // its epoch's star (JointArgs::group) and the single-workgroup update over the stars' views
-  epoch_fn ek_grp = nullptr;
-  void (*uk_grp)(const JointUpdArgs *) = nullptr;
-  // the template mode (lc_joint_fisher_flux_cov): builds of ek (LDS e_lds) and ek_grp that also store the weighted templates
-  epoch_fn ek_tmpl = nullptr, ek_grp_tmpl = nullptr;
-};
-
+// (JointVariant and its builders make_jv, make_jv_cl, make_jv_plain: joint_variants.h)
 struct MregKernels {
   int N;
   void (*mm)(MmBatch);      // batched tiled products of the eight-launch chain (joint_reg_mfma.h)
@@ -218,41 +191,6 @@ int place_psf_stamps(lc_joint *j, const float *psf, int P) {
   return LC_OK;
 }
 
-// BG: also the per-star background forms (lc_joint_create_groups_background) - the sizes of its scope, n <= 32
-template <int N, int SS, int L, int PX, int NW, int LPF = 16, bool BG = true>
-JointVariant make_jv() {
-  typedef JointCfg<N, SS, L, NW, false, LPF> C;
-  JointVariant v{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, joint_update_kernel<N, PX>, N * N / PX,
-                 (int)(StarletLds<N>::FLOATS * sizeof(float)), false, joint_epoch_kernel<C, true>};
-  v.ek_tmpl = joint_epoch_kernel<C, false, 0, false, true>;
-  if constexpr (BG) {
-    v.ek_grp = joint_epoch_kernel<C, false, 0, true>;
-    v.uk_grp = joint_update_groups_uk_kernel<N, PX>;
-    v.ek_grp_tmpl = joint_epoch_kernel<C, false, 0, true, true>;
-  }
-  return v;
-}
-// ... with the cluster form beside it: four-wave workgroups (one wave per SIMD), spectrum in the global scratch
-template <int N, int SS, int L, int PX, int NW, int LPF, int CNW, int CLPF>
-JointVariant make_jv_cl() {
-  // (no per-star background form: n = 64 is outside its scope - the one-star fit runs the cluster form there)
-  JointVariant v = make_jv<N, SS, L, PX, NW, LPF, false>();
-  typedef JointCfg<N, SS, L, CNW, true, CLPF> CC;
-  v.ek_cluster = joint_epoch_kernel<CC, false, 7>;
-  v.cl_lds = CC::LDS_BYTES;
-  v.cl_thr = CC::NTHR;
-  v.cl_lpf = CLPF;
-  return v;
-}
-// stamp sizes beside the tuned ones (any multiple of 8 up to 64 at ss = 2): the same epoch kernel at that N, regulariser and
-// update as the run-time-N multi-block kernels (joint_gm.h) instead of a single-workgroup kernel built per size
-template <int N, int SS, int L, int NW, int LPF = 16>
-JointVariant make_jv_plain() {
-  typedef JointCfg<N, SS, L, NW, false, LPF> C;
-  JointVariant v{C::n, SS, L, joint_epoch_kernel<C>, C::LDS_BYTES, C::NTHR, nullptr, 0, 0, false, joint_epoch_kernel<C, true>};
-  v.ek_tmpl = joint_epoch_kernel<C, false, 0, false, true>;
-  return v;
-}
 // large grids: spectrum scratch in HBM, starlet / update as multi-block kernels
 template <int N, int SS, int L, int NW, int LPF = 16>
 JointVariant make_jv_gm() {
@@ -319,7 +257,7 @@ const JointVariant *find_jv(int n, int ss, int E = 0, int n_cu = 0) {
   };
   for (const auto &v : table)
     if (v.n == n && v.ss == ss) return &v;
-  return nullptr;
+  return ss == 1 ? find_jv_ss1(n) : nullptr;  // (subsampling 1 above 16 x 16: joint_fit_ss1.hip)
 }
 
 __global__ void joint_scene_kernel(int N, int ss, int M, int e, const float *a, const float *cx, const float *cy,
@@ -364,7 +302,6 @@ bool reg_h_on(const lc_joint *j) {
   return lam && (j->free_mask[LC_P_H] || j->h_nonzero);
 }
 
-typedef void (*ps_fn)(JointPsArgs);
 // (tmpl: the template mode's build)
 void find_ps_kernel(int N, int ss, ps_fn *fn, int *lds, bool persist = false, bool tmpl = false) {
   *fn = nullptr;
@@ -382,6 +319,7 @@ void find_ps_kernel(int N, int ss, ps_fn *fn, int *lds, bool persist = false, bo
   LC_PS(112, 2)
   LC_PS(128, 2)
 #undef LC_PS
+  if (!*fn && ss == 1) find_ps_kernel_ss1(N, persist, tmpl, fn, lds);  // (joint_fit_ss1.hip)
 }
 
 // Workgroups per epoch of the cluster form for the next forward + backward launch of this object (0: the one-workgroup

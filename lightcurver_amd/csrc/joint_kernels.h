@@ -1621,11 +1621,13 @@ __global__ __launch_bounds__(C::NTHR) void joint_epoch_kernel(JointArgs A) {
   LC_JSTAMP(8);
 }
 
+#ifndef LC_KERNEL_TEMPLATES_ONLY  // (defined by the translation units that only add instantiations of the templates)
 // the totals as a launch of their own (one block of 64 threads per epoch): when phase D, which computes them otherwise, does not run
 __global__ void joint_epoch_finish_kernel(JointArgs A, int SS, int nparts) {
   __shared__ float TOT[4 + 3 * kMaxSources];
   joint_epoch_totals(A, blockIdx.x, threadIdx.x, SS, nparts, TOT);
 }
+#endif
 
 // ---- kernel 2: ordered reduction over the epochs of this rank -------------------------------------
 // shared = [ dL/dh (N*N) | dL/dc_x (M) | dL/dc_y (M) | sum_e (a - ref) (M) | sum_e (a - ref)^2 (M) | chi2 | n_epochs ]
@@ -1764,12 +1766,14 @@ __device__ __forceinline__ void joint_reduce_block(int bx, int E, int M, int NN,
   __shared__ double lanes[kRedThreads];
   reduce_scalars(E, M, NN, g_cx_e, g_cy_e, chi2_e, a, a_ref, shared, lanes, tid);
 }
+#ifndef LC_KERNEL_TEMPLATES_ONLY  // (defined by the translation units that only add instantiations of the templates)
 __global__ __launch_bounds__(kRedThreads) void joint_reduce_kernel(int E, int M, int NN, int need_h, const float *HG,
                                                                     const float *g_cx_e, const float *g_cy_e,
                                                                     const float *chi2_e, const float *a,
                                                                     const float *a_ref, float *shared) {
   joint_reduce_block((int)blockIdx.x, E, M, NN, need_h, HG, g_cx_e, g_cy_e, chi2_e, a, a_ref, shared);
 }
+#endif
 
 // ---- kernel 3: regularisers, loss, AdaBelief -------------------------------------------------------
 // What the four-launch regulariser chain (joint_reg_fused.h) leaves for its consumer to add up: the sub-gradient as planes

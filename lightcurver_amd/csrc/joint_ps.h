@@ -59,6 +59,22 @@ struct JointPsArgs {
   int e_off;  // first epoch of this launch (a launch over a range of the epochs: batched star photometry, two halves on two streams)
 };
 
+// Strips of LSF data rows a thread takes in the column pass: with one point source their filter outputs (value, d/dX, d/dY:
+// 12 registers per strip) stay in registers up to the residuals.
+constexpr int kPsStrip = 4;
+constexpr int ps_strips(int N, int SS) { return ((N / SS / kPsStrip) * (N / SS) + kPsThreads - 1) / kPsThreads; }
+// Four waves per SIMD (128 registers) where that holds one or two strips: every size at subsampling 2 up to N = 64, and
+// n <= 40 at subsampling 1.  At n = 48, 56, 64 (ss = 1: three and four strips) 128 registers spilled 68 / 120 / 144 bytes per
+// lane, and the three N x n tiles in LDS leave room for three or four workgroups per CU anyway: no limit there.
+constexpr bool ps_four_waves(int N, int SS, bool PERSIST) { return N <= 64 && !PERSIST && ps_strips(N, SS) <= 2; }
+// LDS: the PSF tile [N][N + 1], the two row-pass tiles [N][n + 1], taps and reduction scratch.  All three tiles fit 160 KB up
+// to N = 128 at subsampling 2 and N = 112 at 1; at N = n = 128 (198 KB) the row pass reads the PSF from global memory
+// instead: every row of it once per source, by the threads that would have read it from the tile.
+constexpr int ps_lds_floats(int N, int SS, bool psf_tile) {
+  return (psf_tile ? N * (N + 1) : 0) + 2 * N * (N / SS + 1) + 4 * ntaps(SS) + (kPsThreads / 64 + 1) * (4 + 3 * kMaxSources);
+}
+constexpr bool ps_psf_in_lds(int N, int SS) { return ps_lds_floats(N, SS, true) * (int)sizeof(float) <= 163840; }
+
 // PERSIST: when every free parameter belongs to one epoch (fluxes, shifts, sky levels; the shared positions c_x, c_y held
 // fixed - the reference's default star photometry leaves them free and takes the launch-per-iteration form - and no
 // flux-uniformity / point-source / prior term) the epochs are independent fits, and the whole
@@ -67,13 +83,14 @@ struct JointPsArgs {
 // Same arithmetic per iteration as the launch-per-iteration form (same filters, same reductions, same update).
 // TMPL: the template mode's build (JointArgs::tmpl; not with PERSIST).
 template <int N, int SS, bool PERSIST = false, bool TMPL = false>
-__global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <= 64 && !PERSIST) ? 4 : 1, (N <= 64 && !PERSIST) ? 4 : 8))) void joint_ps_kernel(JointPsArgs P) {
+__global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu(ps_four_waves(N, SS, PERSIST) ? 4 : 1, ps_four_waves(N, SS, PERSIST) ? 4 : 8))) void joint_ps_kernel(JointPsArgs P) {
   constexpr int n = N / SS, NT = ntaps(SS), TS = N + 1, RS = n + 1, nn = n * n, NWV = kPsThreads / 64;
   constexpr int NQ = 4 + 3 * kMaxSources;
   const JointArgs &A = P.J;
   extern __shared__ float plds[];
-  float *Sx = plds;                    // [N][TS]  PSF of the epoch
-  float *R = Sx + N * TS;              // [N][RS]  row pass, value taps
+  constexpr bool SXL = ps_psf_in_lds(N, SS);
+  float *Sx = plds;                    // [N][TS]  PSF of the epoch (SXL; otherwise read where it lies)
+  float *R = Sx + (SXL ? N * TS : 0);  // [N][RS]  row pass, value taps
   float *Rx = R + N * RS;              // [N][RS]  row pass, derivative taps
   float *TAP = Rx + N * RS;            // [4][NT]  tx, dtx, ty, dty
   float *RED = TAP + 4 * NT;           // [NWV + 1][NQ]
@@ -85,7 +102,7 @@ __global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <
   float dxe = A.dx[e], dye = A.dy[e], meane = A.mean[e];
   const float *se = P.psf + (size_t)e * N * N;
   // (16-byte loads: a quarter of the requests; the padded LDS rows take the four values one by one)
-  for (int k4 = tid; k4 < N * N / 4; k4 += kPsThreads) {
+  for (int k4 = tid; k4 < (SXL ? N * N / 4 : 0); k4 += kPsThreads) {
     const float4 v = ((const float4 *)se)[k4];
     float *d = Sx + ((4 * k4) / N) * TS + (4 * k4) % N;
     d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
@@ -120,8 +137,12 @@ __global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <
   // One point source (every star-photometry fit): the filter outputs of a thread's pixels stay in its registers from the
   // column pass to the residuals, instead of travelling through the global scratch F and back (3 n^2 floats each way per
   // epoch and iteration: half of the memory traffic of a batch of thousands of epochs).
-  constexpr int LSF = 4, NITF = ((n / LSF) * n + kPsThreads - 1) / kPsThreads;
-  const bool single = (M == 1);
+  // (up to four strips per thread, n <= 64: the 16 strips of n = 128 at subsampling 1 would be 192 registers - 256 + 124
+  //  accumulation registers, occupancy 1, and 456 bytes of scratch in the persistent form; there the outputs take the way
+  //  through F that several sources take)
+  constexpr int LSF = kPsStrip, NITF = ps_strips(N, SS);
+  constexpr bool REGF = (NITF <= 4);
+  const bool single = REGF && (M == 1);
   float fvr[NITF][LSF], fxr[NITF][LSF], fyr[NITF][LSF];
 #pragma unroll
   for (int t = 0; t < NITF; ++t)
@@ -164,7 +185,7 @@ __global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <
 #pragma unroll
       for (int q = 0; q < WL; ++q) {
         const int v = w0 + q;
-        win[q] = (v >= 0 && v < N) ? Sx[r * TS + v] : 0.f;
+        win[q] = (v >= 0 && v < N) ? (SXL ? Sx[r * TS + v] : se[r * N + v]) : 0.f;
       }
 #pragma unroll
       for (int j = 0; j < LS; ++j) {
@@ -359,6 +380,7 @@ __global__ __launch_bounds__(kPsThreads) __attribute__((amdgpu_waves_per_eu((N <
   }
 }
 
+#ifndef LC_KERNEL_TEMPLATES_ONLY  // (defined by the translation units that only add instantiations of the templates)
 // hist[t0 + it] = sum over the epochs of hist_e[e][it] (lanes stride over the epochs, fixed combine order)
 __global__ void joint_ps_hist_kernel(int E, int T, const float *hist_e, float *hist) {
   const int it = blockIdx.x, lane = threadIdx.x;
@@ -367,11 +389,11 @@ __global__ void joint_ps_hist_kernel(int E, int T, const float *hist_e, float *h
   acc = wave_sum_shfl(acc);
   if (lane == 0) hist[it] = acc;
 }
+#endif
 
 template <int N, int SS>
 constexpr int joint_ps_lds_bytes() {
-  constexpr int n = N / SS, NT = ntaps(SS);
-  return (N * (N + 1) + 2 * N * (n + 1) + 4 * NT + (kPsThreads / 64 + 1) * (4 + 3 * kMaxSources)) * (int)sizeof(float);
+  return ps_lds_floats(N, SS, ps_psf_in_lds(N, SS)) * (int)sizeof(float);
 }
 
 }  // namespace lc

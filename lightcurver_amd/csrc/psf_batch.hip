@@ -14,6 +14,7 @@
 
 #include "psf_kernels.h"
 #include "psf_noise.h"
+#include "psf_variants.h"
 #include "psf_distort.h"
 #include "psf_lbfgs.h"
 
@@ -212,21 +213,7 @@ __global__ void psf_residual_kernel(int S, int n, const float *data, const float
   if (threadIdx.x == 0) redchi2[f] = (float)(C / (K > 0 ? K : 1.0));
 }
 
-typedef void (*psf_kernel_fn)(PsfArgs);
-struct PsfVariant {
-  int n, ss;
-  psf_kernel_fn fn;
-  int nthr, lds_bytes;
-  psf_kernel_fn fn_split;  // two workgroups per frame, or null
-};
-
-template <class C, bool WITH_SPLIT = false>
-PsfVariant make_variant() {
-  psf_kernel_fn split = nullptr;
-  if constexpr (WITH_SPLIT) split = psf_fit_kernel<C, true>;
-  return PsfVariant{C::n, C::SS, psf_fit_kernel<C>, C::NTHR, (int)(C::LDS_FLOATS * sizeof(float)), split};
-}
-
+// (PsfVariant, make_variant: psf_variants.h)
 const PsfVariant *find_variant(int n, int ss) {
   static const PsfVariant table[] = {
       make_variant<PsfCfg<16, 1, 4, 8, true>>(),    // n = 16, ss = 1 (reference test fixture size)
@@ -237,7 +224,7 @@ const PsfVariant *find_variant(int n, int ss) {
   };
   for (const auto &v : table)
     if (v.n == n && v.ss == ss) return &v;
-  return nullptr;
+  return ss == 1 ? find_variant_ss1(n) : nullptr;  // (subsampling 1 above 16 x 16: psf_batch_ss1.hip)
 }
 
 int launch_psf(lc_psf_batch *b, int mode, int n_iter, const lc_adabelief_cfg *cfg, bool want_outputs,
@@ -649,9 +636,9 @@ int lc_psf_batch_set_regularization(lc_psf_batch *b, const float *W, float lam_s
   return LC_OK;
 }
 namespace {
-typedef void (*noise_fn)(int, int, const float *, const float *, const float *, float *);
 noise_fn find_noise_kernel(int N, int ss) {
   if (N == 16 && ss == 1) return psf_noise_accumulate_kernel<16, 1>;
+  if (ss == 1) return find_noise_kernel_ss1(N);
   if (N == 32 && ss == 2) return psf_noise_accumulate_kernel<32, 2>;
   if (N == 48 && ss == 2) return psf_noise_accumulate_kernel<48, 2>;
   if (N == 64 && ss == 2) return psf_noise_accumulate_kernel<64, 2>;

@@ -17,6 +17,7 @@ namespace lc {
 
 constexpr int kNoiseThreads = 256;
 
+#ifndef LC_KERNEL_TEMPLATES_ONLY  // (defined by the translation units that only add instantiations of the templates)
 // tables [F][S][J][3 terms][2: ky, kx][N] (float); block = (frame, star), N threads
 __global__ void psf_noise_tables_kernel(int S, int N, int ss, int J, const float *stars, float *tables) {
   extern __shared__ double nsh[];  // cur[2 axes][N], nxt[2 axes][N]
@@ -74,6 +75,7 @@ __global__ void psf_noise_tables_kernel(int S, int N, int ss, int J, const float
     __syncthreads();
   }
 }
+#endif
 
 // W [F][J][N*N]; block = (frame, scale)
 template <int N, int SS>

@@ -473,8 +473,9 @@ def joint_fit_size(n, ss):
     for m in range(int(n) + 2, 129, 2):
         if l.lc_joint_supported(m, int(ss)):
             return m
-    raise _lib.LcError(f'no joint-fit kernel for {n}x{n} stamps at subsampling {ss} (instantiated at ss = 2: multiples of 8 up '
-                       f'to 64, and 128; other even sizes up to 128 are fitted embedded in the next of these)')
+    raise _lib.LcError(f'no joint-fit kernel for {n}x{n} stamps at subsampling {ss} (instantiated at ss = 1 and ss = 2: multiples '
+                       f'of 8 from 16 to 64, and 128; other even sizes up to 128 are fitted embedded in the next of these; no '
+                       f'other subsampling)')
 
 
 def make_joint_fit(data, sigma2, psf, ss, M, ctx=None):

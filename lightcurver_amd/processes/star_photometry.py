@@ -129,9 +129,13 @@ def do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=2000, uni
       that star's noise maps, ``lam_scales = lam_hf = 3``) - batched as well (``StarPhotometryBatch(background=True)``,
       lc_joint_create_groups_background) where the stamp size's joint fit has a single-workgroup update: n = 16, 24 (the
       reference's default stamp_size_stars), 32 at subsampling 2 and n = 16 at 1, and the even sizes below 32 embedded in the
-      next of these as ``EmbeddedJointFit`` does it (h padded on the way in, cropped on the way out).  Larger stamps (40 - 128:
-      multi-block, cluster and matrix-core forms of the one-star fit) run one star after the other through
-      ``do_one_star_forward_modelling`` - same numbers, no batching gain.
+      next of these as ``EmbeddedJointFit`` does it (h padded on the way in, cropped on the way out).  Larger stamps (40 - 128
+      at subsampling 2, everything above 16 at subsampling 1: multi-block, cluster and matrix-core forms of the one-star fit,
+      or a size whose per-star form is not built) run one star after the other through ``do_one_star_forward_modelling`` -
+      same numbers, no batching gain.
+
+    Without a background the batch runs at every size the joint fit has: n = 16, 24, 32, 40, 48, 56, 64, 128 at subsampling 1
+    and 2, and every other even size up to 128 embedded in the next of these.
 
     Returns one dictionary per star with ALL keys of ``do_one_star_forward_modelling`` (``deconvolved_image``: the scene of the
     star's first epoch, ``starlet_background``: zeros when no background is fitted - what the reference's caller reads at

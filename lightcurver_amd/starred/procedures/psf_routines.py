@@ -45,8 +45,8 @@ def _fit_size(n, ss):
     for m in range(int(n) + 2, 129, 2):
         if l.lc_psf_supported(m, int(ss)):
             return m
-    raise _lib.LcError(f'no PSF kernel for {n}x{n} stamps at subsampling {ss} (instantiated: 16 at ss = 1; 16, 24, 32, 64 at '
-                       f'ss = 2; smaller even sizes are fitted embedded in the next of these)')
+    raise _lib.LcError(f'no PSF kernel for {n}x{n} stamps at subsampling {ss} (instantiated: 16, 32, 64 at ss = 1; 16, 24, 32, '
+                       f'64 at ss = 2; smaller even sizes are fitted embedded in the next of these; no other subsampling)')
 
 
 def build_psf_batch(images, noisemaps, subsampling_factor, masks=None, n_iter_analytic=40,

@@ -117,6 +117,8 @@ def check_evaluation(j, ds, p, n, ss, M, dxy_tol=1e-4, outputs=True):
     po, data, sig2, psf = _oracle_inputs(ds, p)
     model, chi2_e = j.model()
     mo = om.deconv_model(po, psf, ss, n)
+    print(f'evaluation n={n} ss={ss}: model {H.rel_err(model, mo.numpy()):.2e} chi2 per epoch '
+          f'{H.rel_err(chi2_e, (((data - mo) ** 2) / sig2).sum((-1, -2)).numpy()):.2e}')
     assert H.rel_err(model, mo.numpy()) < 3e-5
     assert H.rel_err(chi2_e, (((data - mo) ** 2) / sig2).sum((-1, -2)).numpy()) < 3e-5
     W = om.propagate_noise_deconv(sig2, psf, ss)
@@ -132,6 +134,8 @@ def check_evaluation(j, ds, p, n, ss, M, dxy_tol=1e-4, outputs=True):
         j.set_loss(**cfg)
         L, g = oo.value_and_grad(fn, po, FREE)
         loss, grads = j.loss_grad(FREE)
+        print(f'evaluation n={n} ss={ss} leg {i}: loss {abs(loss - float(L)) / abs(float(L)):.2e}',
+              {k: '%.2e' % H.rel_err(grads[k], g[k].numpy()) for k in FREE}, f'ring of h {ring_rel_err(grads["h"], g["h"].numpy(), N):.2e}')
         assert abs(loss - float(L)) / abs(float(L)) < 3e-5, (i, loss, float(L))
         for k in FREE:
             assert H.rel_err(grads[k], g[k].numpy()) < (dxy_tol if k in ('dx', 'dy') else 1e-4), (i, k)
@@ -159,7 +163,12 @@ def debug_global():
 @pytest.mark.parametrize('n,ss,geom', [(16, 1, 'rot1'), (16, 1, 'trans'),
                                        (16, 2, 'rot1'), (16, 2, 'rot2'), (16, 2, 'rot3'), (16, 2, 'trans'),
                                        (24, 2, 'rot2'), (32, 2, 'rot1'), (32, 2, 'rot3'), (32, 2, 'trans'),
-                                       (40, 2, 'rot2'), (48, 2, 'rot3'), (56, 2, 'rot1'), (64, 2, 'rot2'), (64, 2, 'trans')])
+                                       (40, 2, 'rot2'), (48, 2, 'rot3'), (56, 2, 'rot1'), (64, 2, 'rot2'), (64, 2, 'trans'),
+                                       # subsampling 1 (no binned rows: the branch beside FOLD): the sizes whose transforms
+                                       # run over 8 lanes, then those over 16
+                                       (24, 1, 'rot1'), (24, 1, 'rot2'), (24, 1, 'trans'), (40, 1, 'rot2'), (40, 1, 'trans'),
+                                       (56, 1, 'rot3'), (56, 1, 'trans'),
+                                       (32, 1, 'rot3'), (48, 1, 'rot1'), (64, 1, 'rot2'), (64, 1, 'trans')])
 def test_default_kernels(ctx, monkeypatch, n, ss, geom):
     monkeypatch.delenv('LCMI_N128_SPLIT', raising=False)
     alphas, shifts = GEOM[geom]
@@ -202,9 +211,40 @@ def test_n128_two_epochs(ctx):
     j.close()
 
 
+def test_n128_two_epochs_at_subsampling_1(ctx, monkeypatch):
+    """n = 128 at subsampling 1 (N = 128: the one-workgroup epoch kernel and its cluster form) at the angles and shifts
+    above.  The cluster form runs inside the library's own loops only (cluster_parts), so beside the single evaluation -
+    dx / dy at the bound of test_n128_two_epochs, for its reason: fp32 sums over a 128 x 128 stamp - five iterations of the
+    device loop run in the form the object selects for two epochs (several workgroups per epoch, which must not fall back)
+    and, with LCMI_CLUSTER=0, in the one-workgroup kernel, each against one oracle trajectory."""
+    monkeypatch.delenv('LCMI_N128_SPLIT', raising=False)
+    monkeypatch.delenv('LCMI_CLUSTER', raising=False)
+    alphas, shifts = [120.0, 180.0], [(2.71, -0.28), (-5.3, -4.7)]
+    ds, p = geometry_problem(128, 1, alphas, shifts, 978)
+    j = _joint(ctx, ds, p, 1, 2)
+    check_evaluation(j, ds, p, 128, 1, 2, dxy_tol=3e-4, outputs=False)
+    j.close()
+    T = 5
+    ds, p = _trajectory_problem(128, 979, alphas, shifts, ss=1)
+    ref = oracle_trajectory(ds, p, T, ss=1)
+    j = _joint(ctx, ds, p, 1, 2)
+    info = check_trajectory(j, ds, p, 128, T, ss=1, ref=ref)
+    j.close()
+    assert info[0] >= 2 and info[1] == 0, info       # several workgroups per epoch, no fall-back
+    monkeypatch.setenv('LCMI_CLUSTER', '0')
+    j = _joint(ctx, ds, p, 1, 2)
+    info = check_trajectory(j, ds, p, 128, T, ss=1, ref=ref)
+    j.close()
+    assert tuple(info) == (0, 0), info
+
+
+# ROT_1's shift of each angle
 @pytest.mark.parametrize('n,ss,alphas,shifts', [(16, 2, [0.0, 120.0, 180.0], [(0.37, -0.21), (2.6, -0.3), (-5.3, -4.7)]),
                                                 (16, 1, [0.0, 180.0, 120.0], [(0.0, 0.0), (-2.6, 3.4), (5.3, 2.6)]),
-                                                (32, 2, [0.0, 180.0, 120.0], [(0.0, 0.0), (-5.3, -4.7), (2.6, -0.3)])])
+                                                (32, 2, [0.0, 180.0, 120.0], [(0.0, 0.0), (-5.3, -4.7), (2.6, -0.3)])] +
+                         # subsampling 1: one or two strips per thread (24), four strips without the four-wave limit (64),
+                         # outputs and PSF through global memory (128)
+                         [(n, 1, [0.0, 180.0, 120.0], [(0.37, -0.21), (-5.3, -4.7), (2.71, -0.28)]) for n in (24, 64, 128)])
 def test_point_source_only_path(ctx, n, ss, alphas, shifts):
     """h == 0 and fixed (csrc/joint_ps.h) at 120 and 180 degrees: model, loss, gradients and Fisher flux errors."""
     M = 2
@@ -220,48 +260,63 @@ def test_point_source_only_path(ctx, n, ss, alphas, shifts):
     assert H.rel_err(chi2_e, (((data - mo) ** 2) / sig2).sum((-1, -2)).numpy()) < 3e-5
     L, g = oo.value_and_grad(lambda q: om.deconv_loss(q, data, sig2, psf, ss, lam_pos_ps=5.0, lam_fu=0.4), po, free)
     loss, grads = j.loss_grad(free)
+    fisher = H.rel_err(j.fisher_flux_sigma(), om.fisher_flux_sigma(po, sig2, psf, ss).numpy())
+    j.close()
+    print(f'point sources only n={n} ss={ss}: model {H.rel_err(model, mo.numpy()):.2e} loss {abs(loss - float(L)) / abs(float(L)):.2e}',
+          {k: '%.2e' % H.rel_err(grads[k], g[k].numpy()) for k in free}, f'fisher {fisher:.2e}')
     assert abs(loss - float(L)) / abs(float(L)) < 3e-5
     for k in free:
         assert H.rel_err(grads[k], g[k].numpy()) < 1e-4, k
-    assert H.rel_err(j.fisher_flux_sigma(), om.fisher_flux_sigma(po, sig2, psf, ss).numpy()) < 3e-5
-    j.close()
+    assert fisher < 3e-5
 
 
-def _trajectory_problem(n, seed, alphas, shifts):
+def _trajectory_problem(n, seed, alphas, shifts, ss=2):
     # the jitter of test_joint_gpu's trajectories (a background close to the truth): a pixel moves by at most T * lr
-    ds, p = geometry_problem(n, 2, alphas, shifts, seed, rough=False)
+    ds, p = geometry_problem(n, ss, alphas, shifts, seed, rough=False)
     rng = np.random.default_rng(seed + 2)
     p['h'] = (p['h'] * rng.uniform(0.8, 1.2, p['h'].shape) + 2e-3 * rng.standard_normal(p['h'].shape))
     p['h'] = p['h'].astype(np.float32).astype(np.float64)
     return ds, p
 
 
-def check_trajectory(j, ds, p, n, T, lr=1e-3):
-    """T AdaBelief iterations of the device loop against oo.adabelief; the ring of h as tight as the interior.  Returns
-    cluster_info() of the run."""
-    N = 2 * n
+TRAJ_LAMS = dict(lam_scales=1.0, lam_hf=1.0, lam_pos=10.0, lam_pts=0.01, lam_fu=1.0)
+
+
+def oracle_trajectory(ds, p, T, lr=1e-3, ss=2):
+    """-> (W, loss history (T + 1,), final parameters) of oo.adabelief on the loss check_trajectory sets."""
     po, data, sig2, psf = _oracle_inputs(ds, p)
-    W = om.propagate_noise_deconv(sig2, psf, 2)
+    W = om.propagate_noise_deconv(sig2, psf, ss)
+    pf, lh, l0 = oo.adabelief(lambda q: om.deconv_loss(q, data, sig2, psf, ss, W=W, **TRAJ_LAMS), po, FREE, lr, T, schedule=True)
+    return W, np.array([l0] + lh), pf
+
+
+def check_trajectory(j, ds, p, n, T, lr=1e-3, ss=2, ref=None):
+    """T AdaBelief iterations of the device loop against oo.adabelief (`ref`: oracle_trajectory of the same problem, where
+    several runs share it); the ring of h as tight as the interior.  Returns cluster_info() of the run."""
+    N = ss * n
+    W, ref, pf = ref if ref is not None else oracle_trajectory(ds, p, T, lr, ss)
     j.set_params(**p)
     j.set_loss(W=W.numpy(), lam_scales=1.0, lam_hf=1.0, lam_positivity=10.0, lam_pts_source=0.01, lam_flux_uniformity=1.0)
     j.set_free(FREE)
     j.run_adabelief(T, init_learning_rate=lr, schedule_learning_rate=True)
     info = j.cluster_info()
     hist = j.loss_history()
-    fn = lambda q: om.deconv_loss(q, data, sig2, psf, 2, W=W, lam_scales=1.0, lam_hf=1.0, lam_pos=10.0, lam_pts=0.01,
-                                  lam_fu=1.0)
-    pf, lh, l0 = oo.adabelief(fn, po, FREE, lr, T, schedule=True)
-    ref = np.array([l0] + lh)
+    got = j.get_params()
+    dh = np.abs(got['h'] - pf['h'].numpy()).reshape(N, N)
+    m = ring_mask(N)
+    ring, inner = dh[m], dh[~m]
+    print(f'trajectory n={n} ss={ss} T={T} cluster_info {tuple(info)}:',
+          dict(hist='%.2e' % (np.abs(hist - ref).max() / np.abs(ref).max()), a='%.2e' % H.rel_err(got['a'], pf['a'].numpy()),
+               c_x='%.2e' % np.abs(got['c_x'] - pf['c_x'].numpy()).max(), dx='%.2e' % np.abs(got['dx'] - pf['dx'].numpy()).max(),
+               dy='%.2e' % np.abs(got['dy'] - pf['dy'].numpy()).max(), dh_max='%.2e' % dh.max(), dh_med='%.2e' % np.median(dh),
+               ring_med='%.2e' % np.median(ring), ring_p95='%.2e' % np.percentile(ring, 95),
+               inner_p95='%.2e' % np.percentile(inner, 95)))
     assert hist.shape == (T + 1,)
     assert np.abs(hist - ref).max() / np.abs(ref).max() < 2e-4
-    got = j.get_params()
     assert H.rel_err(got['a'], pf['a'].numpy()) < 2e-4
     assert np.abs(got['c_x'] - pf['c_x'].numpy()).max() < 5e-4
     assert np.abs(got['dx'] - pf['dx'].numpy()).max() < 5e-4
     assert np.abs(got['dy'] - pf['dy'].numpy()).max() < 5e-4
-    dh = np.abs(got['h'] - pf['h'].numpy()).reshape(N, N)
-    m = ring_mask(N)
-    ring, inner = dh[m], dh[~m]
     assert dh.max() < 0.05 * T * lr and np.median(dh) < 1e-5
     # a ring that follows another gradient drifts by up to lr per iteration in most of its pixels: its median and 95th
     # percentile must be those of the interior, where only the odd sign flip of a ~0 starlet coefficient shows
@@ -280,6 +335,19 @@ def test_n64_device_loop_mixed_angles(ctx, monkeypatch, cluster):
     j = _joint(ctx, ds, p, 2, 2)
     assert check_trajectory(j, ds, p, 64, 20) == (int(cluster), 0)
     j.close()
+
+
+@pytest.mark.parametrize('n', [24, 56, 64])
+def test_device_loop_mixed_angles_at_subsampling_1(ctx, monkeypatch, n):
+    """20 iterations of ROT_1 at subsampling 1: n = 24 and 56 (transforms over 8 lanes; regulariser, reduction and update of
+    the run-time-N kernels inside the loop) and n = 64 (16 lanes, single-workgroup update); ring against interior as above."""
+    monkeypatch.delenv('LCMI_N128_SPLIT', raising=False)
+    monkeypatch.delenv('LCMI_CLUSTER', raising=False)
+    ds, p = _trajectory_problem(n, 985 + n, *ROT_1, ss=1)
+    j = _joint(ctx, ds, p, 1, 2)
+    info = check_trajectory(j, ds, p, n, 20, ss=1)
+    j.close()
+    assert info[1] == 0, info
 
 
 def test_rotation_flag_follows_alpha(ctx, monkeypatch, debug_global):

@@ -12,6 +12,7 @@ from tests import helpers as H
 from tests import test_joint_gpu as TJ
 from tests import test_fisher_positions_gpu as FP
 from tests import test_fisher_shifts_gpu as FS
+from tests import test_fisher_covariance_gpu as FC
 from tests import test_joint_psf_size_gpu as PS
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +65,9 @@ def test_no_background_path_two_sources(ctx):
         assert H.rel_err(grads[k], g[k].numpy()) < 1e-4, k
 
 
-@pytest.mark.parametrize('E,n,ss', [(3, 32, 1), (2, 64, 1)])
+@pytest.mark.parametrize('E,n,ss', [(3, 32, 1), (2, 64, 1),
+                                    # the ek_aux build of the epoch kernel with transforms over 8 lanes
+                                    (3, 24, 1), (2, 40, 1), (2, 56, 1)])
 def test_noise_propagation_and_fisher(ctx, monkeypatch, E, n, ss):
     ds, j, po, data, sig2, psf = TJ._setup(ctx, E, 2, n, ss, 11 + n)
     monkeypatch.delenv('LCMI_NOISE_HOST', raising=False)
@@ -78,10 +81,12 @@ def test_noise_propagation_and_fisher(ctx, monkeypatch, E, n, ss):
     monkeypatch.setenv('LCMI_NOISE_HOST', '1')
     Wh = j.propagate_noise()
     monkeypatch.delenv('LCMI_NOISE_HOST')
-    assert H.rel_err(Wh, Wo) < 3e-5
     s = j.fisher_flux_sigma()
     j.close()
-    assert H.rel_err(s, om.fisher_flux_sigma(po, sig2, psf, ss).numpy()) < 3e-5
+    so = om.fisher_flux_sigma(po, sig2, psf, ss).numpy()
+    print(f'noise n={n}: host W {H.rel_err(Wh, Wo):.2e}, fisher_flux_sigma {H.rel_err(s, so):.2e}')
+    assert H.rel_err(Wh, Wo) < 3e-5
+    assert H.rel_err(s, so) < 3e-5
 
 
 def _trajectory(ctx, E, M, n, ss, with_h, T, seed):
@@ -113,7 +118,9 @@ def _judge_trajectory(hist, got, ref, pf, T, with_h, tag):
         assert fig['dh_max'] < 0.05 * T * 1e-3 and fig['dh_med'] < 1e-5
 
 
-@pytest.mark.parametrize('n,ss,with_h', [(32, 1, True), (64, 1, True), (24, 1, False)])
+@pytest.mark.parametrize('n,ss,with_h', [(32, 1, True), (64, 1, True), (24, 1, False),
+                                         # h free at the sizes of the run-time-N update (8-lane transforms)
+                                         (24, 1, True), (40, 1, True), (56, 1, True)])
 def test_adabelief_trajectory(ctx, n, ss, with_h):
     T = 25
     hist, got, info, ref, pf = _trajectory(ctx, 4, 2, n, ss, with_h, T, 40 + n)
@@ -194,8 +201,8 @@ def _normalised_error(dense, Fo):
     return float(np.abs(dense / nrm - Fo / nrm).max())
 
 
-def test_fisher_with_positions_free(ctx):
-    E, M, n, ss = 3, 2, 32, 1
+def _positions_free(ctx, n):
+    E, M, ss = 3, 2, 1
     ds, p, sig2 = FP._problem(n, ss, M, 900 + n + ss + M, True, E=E)
     Fo = FP._oracle_fisher(ds, p, sig2, ss)
     j = FP._joint(ctx, ds, sig2, p, ss, M)
@@ -213,9 +220,17 @@ def test_fisher_with_positions_free(ctx):
     assert err_C < 3e-6 * cond + 1e-6
 
 
-@pytest.mark.parametrize('positions', [False, True], ids=['c-fixed', 'c-prior'])
-def test_fisher_with_shifts_free(ctx, positions):
-    E, M, n, ss = 3, 2, 32, 1
+def test_fisher_with_positions_free(ctx):
+    _positions_free(ctx, 32)
+
+
+@pytest.mark.parametrize('n', [24, 56])
+def test_fisher_with_positions_free_at_the_8_lane_sizes(ctx, n):
+    _positions_free(ctx, n)
+
+
+def _shifts_free(ctx, positions, n):
+    E, M, ss = 3, 2, 1
     ds, p, sig2, Fo = _shift_case(n, ss, M)
     j = FS._joint(ctx, ds, sig2, p, ss, M, prior=FS._prior(p) if positions else None)
     try:
@@ -233,6 +248,17 @@ def test_fisher_with_shifts_free(ctx, positions):
     assert err_C < 3e-6 * cond + 1e-6
 
 
+@pytest.mark.parametrize('positions', [False, True], ids=['c-fixed', 'c-prior'])
+def test_fisher_with_shifts_free(ctx, positions):
+    _shifts_free(ctx, positions, 32)
+
+
+@pytest.mark.parametrize('n', [24, 56])
+@pytest.mark.parametrize('positions', [False, True], ids=['c-fixed', 'c-prior'])
+def test_fisher_with_shifts_free_at_the_8_lane_sizes(ctx, positions, n):
+    _shifts_free(ctx, positions, n)
+
+
 _SHIFT_CASES = {}
 
 
@@ -246,8 +272,32 @@ def _shift_case(n, ss, M):
     return _SHIFT_CASES[(n, ss, M)]
 
 
+def test_flux_covariance_with_a_background_at_24(ctx):
+    """fisher_flux_covariance through the template mode of the 8-lane epoch kernel (h non-zero: the FFT pipeline) at n = 24,
+    three sources, masked pixels, epochs at 0, 120 and 180 degrees: the comparison of tests/test_fisher_covariance_gpu.py
+    (3e-5 on every block of F against the oracle's Hessian, 3e-6 cond + 1e-6 on its inverse)."""
+    n, ss, M = 24, 1, 3
+    ds, p, sig2 = FC._problem(n, ss, M, 700 + n + ss + M, True, E=3)
+    Hm = FC._oracle_hessian(ds, p, sig2, ss)
+    j = FC._joint(ctx, ds, sig2, p, ss, M)
+    try:
+        F, Cv, _ = j.fisher_flux_covariance()
+        blocks = [Hm[e * M:(e + 1) * M, e * M:(e + 1) * M] for e in range(3)]
+        print(f'flux covariance n={n} ss={ss}: F', ['%.2e' % H.rel_err(F[e], blocks[e]) for e in range(3)],
+              'C', ['%.2e (cond %.3g)' % (H.rel_err(Cv[e], np.linalg.inv(blocks[e])), np.linalg.cond(blocks[e])) for e in range(3)])
+        FC._check_against_oracle(j, ds, p, sig2, ss, M)
+    finally:
+        j.close()
+
+
 # ---- PSF stamps of another side ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('P', [24, 40])
 def test_psf_stamps_of_another_side(ctx, P):
     """N = 32 at subsampling 1 with 24-wide stamps (placed exactly) and 40-wide ones (windowed to the grid)."""
     PS._check_model_loss_and_gradients(ctx, 3, 2, 32, 1, P)
+
+
+@pytest.mark.parametrize('n,P', [(24, 32), (40, 24)])
+def test_psf_stamps_of_another_side_at_the_8_lane_sizes(ctx, n, P):
+    """The grids of the 8-lane transforms: N = 24 with 32-wide stamps (windowed), N = 40 with 24-wide ones (placed)."""
+    PS._check_model_loss_and_gradients(ctx, 3, 2, n, 1, P)

@@ -133,7 +133,7 @@ def test_float32_port_distance_per_term(case, with_h, base, terms, free):
         L1, g1 = _port_eval(c, pt, base)
         for t in terms:
             if t not in PORT_TERMS:
-                assert (t, case[2]) not in JT.R_GRAD and (t, case[2]) not in JT.R_LOSS
+                assert JT.r_key(t, case) not in JT.R_GRAD and JT.r_key(t, case) not in JT.R_LOSS
                 continue
             L0, g0 = _port_eval(c, pt, tuple(u for u in base if u != t))
             dL, dg = JT.oracle_term(pt, t, free, base=base)
@@ -142,9 +142,9 @@ def test_float32_port_distance_per_term(case, with_h, base, terms, free):
             print(f'{case} {t}: float32 port value {dist_L:.1e} gradient {dist_g:.1e}')
             assert np.isfinite(dist_L) and np.isfinite(dist_g)
             assert JT.R_DEFAULT <= JT.r_grad(t, case) <= JT.R_CAP and JT.RL_DEFAULT <= JT.r_loss(t, case) <= JT.R_CAP
-            if (t, case[2]) in JT.R_GRAD:
-                assert JT.R_GRAD[(t, case[2])] <= 4 * dist_g, (t, dist_g)
-            if (t, case[2]) in JT.R_LOSS:
-                assert JT.R_LOSS[(t, case[2])] <= 4 * dist_L, (t, dist_L)
+            if JT.r_key(t, case) in JT.R_GRAD:
+                assert JT.R_GRAD[JT.r_key(t, case)] <= 4 * dist_g, (t, dist_g)
+            if JT.r_key(t, case) in JT.R_LOSS:
+                assert JT.R_LOSS[JT.r_key(t, case)] <= 4 * dist_L, (t, dist_L)
     finally:
         c.close()

@@ -88,12 +88,13 @@ def test_one_workgroup_update(ctx, case, monkeypatch):
         j.close()
 
 
-@pytest.mark.parametrize('case,forced', [(JT.CASE_MULTI_BLOCK, False), (JT.CASE_N128, False)] + [(c, True) for c in JT.CASES_FORCED_GLOBAL],
-                         ids=str)
+@pytest.mark.parametrize('case,forced', [(JT.CASE_MULTI_BLOCK, False), (JT.CASE_N128, False)] + [(c, True) for c in JT.CASES_FORCED_GLOBAL] +
+                         [(c, False) for c in JT.CASES_MULTI_BLOCK_SS1 + [JT.CASE_N128_SS1]], ids=str)
 def test_multi_block_update(ctx, case, forced):
     """n = 40 and 64 take the multi-block update by themselves (through loss_grad the regulariser comes from the
     multi-block cascade kernels at n = 40 and from the matrix-core chain at N = 128); n = 16 and 32 under
-    lc_joint_set_debug_global."""
+    lc_joint_set_debug_global.  At subsampling 1: n = 24, 40, 56 (run-time-N regulariser and update behind the epoch kernel
+    with 8-lane transforms) and n = 128 (the chain)."""
     from lightcurver_amd import _lib
     lib = _lib.lib()
     pt = JT.point_of(case)
@@ -110,21 +111,36 @@ def test_multi_block_update(ctx, case, forced):
             lib.lc_joint_set_debug_global(0)
 
 
-@pytest.mark.parametrize('base', [JT.ALL, ('pos', 'pts')], ids=['all-terms', 'no-l1'])
-@pytest.mark.parametrize('env', [{}, {'LCMI_REG_FUSED': '0'}, {'LCMI_REG_CASCADE': '1'}], ids=['default', 'eight-launch', 'cascade'])
+CHAIN_ENVS = dict(argvalues=[{}, {'LCMI_REG_FUSED': '0'}, {'LCMI_REG_CASCADE': '1'}], ids=['default', 'eight-launch', 'cascade'])
+CHAIN_BASES = dict(argvalues=[JT.ALL, ('pos', 'pts')], ids=['all-terms', 'no-l1'])
+
+
+@pytest.mark.parametrize('base', **CHAIN_BASES)
+@pytest.mark.parametrize('env', **CHAIN_ENVS)
 def test_large_grid_regulariser_chains(ctx, monkeypatch, env, base):
     """N = 128: the regulariser through the four-launch matrix-core chain, the eight-launch one, the cascade; with both l1
     strengths zero the eight-launch form is the production path.  Evaluated as an iteration does it: step_local (the chain
     on the second stream) + step_grad."""
+    _check_chains(ctx, monkeypatch, env, base, JT.CASE_N128)
+
+
+@pytest.mark.parametrize('base', **CHAIN_BASES)
+@pytest.mark.parametrize('env', **CHAIN_ENVS)
+def test_large_grid_regulariser_chains_at_subsampling_1(ctx, monkeypatch, env, base):
+    """The same chains behind the N = 128 epoch kernel of subsampling 1 (n = 128)."""
+    _check_chains(ctx, monkeypatch, env, base, JT.CASE_N128_SS1)
+
+
+def _check_chains(ctx, monkeypatch, env, base, case):
     for k in ('LCMI_REG_FUSED', 'LCMI_REG_CASCADE', 'LCMI_REG_DENSE', 'LCMI_PTS_TAIL', 'LCMI_PTS_CHAIN'):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    pt = JT.point_of(JT.CASE_N128)
+    pt = JT.point_of(case)
     terms = tuple(t for t in JT.N128_TERMS if t in base)
     j = _fit(ctx, pt, JT.FREE_H)
     try:
-        _check_terms(j, pt, JT.CASE_N128, base, terms, JT.FREE_H, how='step')
+        _check_terms(j, pt, case, base, terms, JT.FREE_H, how='step')
     finally:
         j.close()
 
@@ -207,8 +223,8 @@ def _against_the_oracle(label, got, ref, free, T=JT.T_LOOP):
 @pytest.mark.parametrize('term', JT.ALL)
 @pytest.mark.parametrize('case', [c for c, _ in JT.LOOP_SECOND_STREAM], ids=str)
 def test_loop_with_second_stream_regulariser(ctx, case, term):
-    """n = 16, 32: inside lc_joint_run_adabelief the regulariser and the point-source term run on the second stream ahead of
-    the single-workgroup update (reg_mode 1 / 2, pts_early)."""
+    """n = 16, 32 (and n = 32, 48 at subsampling 1): inside lc_joint_run_adabelief the regulariser and the point-source term
+    run on the second stream ahead of the single-workgroup update (reg_mode 1 / 2, pts_early)."""
     pt = JT.point_of(case)
     got = _run(ctx, pt, (term,), JT.FREE_H)
     _against_the_oracle(f'{case} {term}', got, JT.oracle_trajectory(pt, (term,), JT.FREE_H), JT.FREE_H)
@@ -216,7 +232,8 @@ def test_loop_with_second_stream_regulariser(ctx, case, term):
 
 @pytest.mark.parametrize('case,term', [(c, t) for c, terms in JT.LOOP_FUSED for t in terms], ids=str)
 def test_loop_with_fused_reduction_and_update(ctx, monkeypatch, case, term):
-    """n = 40, 64: reduction over the epochs and update in one launch; as two kernels (LCMI_SPLIT_UPDATE=1) the same bits."""
+    """n = 40, 64 (and n = 24, 40, 56 at subsampling 1, every term): reduction over the epochs and update in one launch; as two
+    kernels (LCMI_SPLIT_UPDATE=1) the same bits."""
     monkeypatch.delenv('LCMI_SPLIT_UPDATE', raising=False)
     pt = JT.point_of(case)
     got = _run(ctx, pt, (term,), JT.FREE_H)

@@ -183,3 +183,35 @@ def read_roi_file(roi_file):
         raise ValueError('data / noisemap / psf shapes are inconsistent')
     out['psf_side'] = int(psf.shape[1])
     return out
+
+
+def write_roi_file(node, prepared, **metadata):
+    """The datasets of roi_file_preparation.py:215-229 into ``node`` (an open, writable h5py file / group, or a mapping), so
+    that ``read_roi_file(node)`` reads them back.  ``prepared``: what ``processes.roi_file_preparation.prepare_roi_cutouts``
+    returns (data, noisemap, psf, relative_normalization_error; kept -> frame_id and mjd unless given).  ``metadata``: any
+    other name of ROI_FILE_KEYS - per-frame arrays in the order of ``prepared`` (index the caller's tables with
+    ``prepared['kept']``), scalars for global_zeropoint and global_zeropoint_scatter; a scalar ``subsampling_factor`` is
+    repeated per frame (``read_roi_file`` requires the dataset).  Returns ``node``."""
+    unknown = set(metadata) - set(ROI_FILE_KEYS)
+    if unknown:
+        raise KeyError(f'unknown ROI file datasets {sorted(unknown)}; known: {ROI_FILE_KEYS}')
+    E = len(prepared['data'])
+    values = {'frame_id': prepared['kept'], 'data': prepared['data'], 'noisemap': prepared['noisemap'], 'psf': prepared['psf'],
+              'relative_normalization_error': prepared['relative_normalization_error']}
+    if 'mjd' in prepared:
+        values['mjd'] = prepared['mjd']
+    values.update({k: v for k, v in metadata.items() if v is not None})
+    if 'subsampling_factor' in values and np.ndim(values['subsampling_factor']) == 0:
+        values['subsampling_factor'] = np.full(E, values['subsampling_factor'])
+    for key in ROI_FILE_KEYS:
+        if key not in values:
+            continue
+        v = np.array(values[key])
+        if key in ('global_zeropoint', 'global_zeropoint_scatter'):
+            v = np.array(float(v))
+        elif v.shape[:1] != (E,):
+            raise ValueError(f'{key}: expected one entry per prepared frame ({E}), got shape {v.shape}')
+        if key in node.keys():
+            del node[key]
+        node[key] = v
+    return node

@@ -30,6 +30,15 @@
 #ifndef LC_SERIAL_TRIM
 #define LC_SERIAL_TRIM 1  // C2, two workgroups: role 0 publishes straight behind P5 and writes T of the next iteration behind its pixel step
 #endif
+// DESIGN.md, "PSF fit: the next wave task's row pass under the transposed column pass"
+// (make alt ALTFLAGS=-DLC_TASK_AHEAD=0 for the task loop before it; the second switch follows the first unless it is given, for
+// the runs recorded there of either half alone)
+#ifndef LC_TASK_AHEAD
+#define LC_TASK_AHEAD 1  // C2, two workgroups: a wave runs the row pass of its next task among the transposed column pass of this one
+#endif
+#ifndef LC_V_ZERO_ONCE
+#define LC_V_ZERO_ONCE LC_TASK_AHEAD  // C2, two workgroups: role 0 writes the zero columns of V once per launch, not in every edge task
+#endif
 namespace lc {
 constexpr int kXFlagStride = 16;   // flag words per (frame, role): word 0 is the flag, the rest keeps (frame, role) pairs on lines of their own
 
@@ -401,6 +410,23 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
   constexpr bool TRIM = SPLIT && C::WC && PX == 8 && LC_SERIAL_TRIM;
   static_assert(!TRIM || 3 * C::MAXS <= kWave, "the x0 sums and the stars' step are lanes of one wave");
   [[maybe_unused]] float tpix_next[TRIM ? PX : 1];
+  // The same kernel's wave tasks ("PSF fit: the next wave task's row pass under the transposed column pass").
+  // * TASK_AHEAD: the task loop of role 0 is a software pipeline over the wave's own tasks (at the loop).
+  // * V_ZERO_ONCE: the zero columns on either side of V's data columns are written here, once per launch.  The edge tasks rewrite
+  //   them in every iteration only because the starlet reuses the region, and role 0 of this form never runs the starlet: nothing
+  //   but the transposed column pass, which keeps to the data columns, writes there.  Visible to P5 behind the barrier that ends the
+  //   wave tasks.  The two belong together: the edge tasks' writes are two branches at the end of the transposed pass, and the
+  //   pipelined stretch is one basic block only without them (measured: either alone gains about one run-to-run spread, the pair four).
+  constexpr bool C2_SPLIT = SPLIT && C::WC && PX == 8;
+  constexpr bool TASK_AHEAD = C2_SPLIT && LC_TASK_AHEAD, V_ZERO_ONCE = C2_SPLIT && LC_V_ZERO_ONCE;
+  if constexpr (V_ZERO_ONCE) {
+    if (role == 0) {
+      for (int i = tid0; i < SG * N; i += NTHR) {
+        V[i * C::VS] = 0.f;
+        V[i * C::VS + n + 1] = 0.f;
+      }
+    }
+  }
   if constexpr (TRIM) {
     if (role == 0) {
       const int pu = tid0 / (N / PX), pv = (tid0 % (N / PX)) * PX;
@@ -478,6 +504,189 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         // after ~17.5 k, running alone - at 1 / 1.75 of the pair's rate - for the rest; tools/psf_stamps.py prints the times.
         // Measured and left out: handing the tasks out from an LDS counter.  With four tasks of 3.5 k cycles per wave the
         // older waves simply take a fifth one each and the phase ends at the same time: 16.2 against 15.9 us per iteration.)
+        if constexpr (TASK_AHEAD) {
+          // C2 in the two-workgroup form: a software pipeline over the wave's own tasks (task = wid, wid + NW, ...).  A task is
+          // three passes of one item per lane, each waiting for the LDS round trip of the one before, and only the other wave of
+          // the SIMD fills those waits.  The row pass of the wave's next task and the transposed column pass of this one have no
+          // operand in common, so they are issued as one stretch: all reads of both in front, the row pass's multiply-adds over
+          // the transposed pass's round trip, one wave_lds_sync behind both.  The first task's row pass stands in front of the
+          // loop, the last task's transposed pass stands alone.  Operands, the lanes' items and the order of every sum are those
+          // of the loop below: the same bits (tests/test_psf_task_ahead_gpu.py).
+          // Why the LDS order is safe:
+          // * the LDS operations of one wave execute in order, and the column pass of task k has its windows of R2w in registers
+          //   in front of its wave_lds_sync, so the R2w writes of task k + 1's row pass cannot pass them;
+          // * the aprons of R2w are never written, by either form;
+          // * a row pass reads T and the tap tables, which do not change during the phase, and writes the wave's R2w: it touches
+          //   neither RESw nor V, the transposed pass touches nothing else.
+          static_assert(SS == 2 && N == kWave && JB * (n / LC) == kWave && LA == LC, "one item per lane in each pass of a task");
+          constexpr int NP = (NT + 1) / 2, WL2 = (JB - 1) + NP, WL = SS * (LC - 1) + NT, WI = (SS * LA - 1 + NT - 1) / SS + 1;
+          const int jl = lane % JB, a0 = (lane / JB) * LC;  // column pass and transposed pass: the lane's column and first data row
+          // (tasks of stars >= S are skipped, wave-uniform: they are the last ones, tasks are ordered by star)
+          const int ntask = min(SG, S - g0) * NBLK;
+          float dpre[LC], wpre[LC];        // data / weights of the task whose row pass ran last
+          lc_v2f tr2[NP], win2[WL2];       // row pass: paired x taps, window of T
+          lc_v2f py[NP];                   // transposed pass: paired y taps, residual column
+          float rv[WI];
+          auto pixel_request = [&](int task) {
+            const int s = g0 + task / NBLK, jd0 = (task % NBLK) * JB;
+#pragma unroll
+            for (int j = 0; j < LC; ++j) {
+              const size_t pix = (size_t)s * n * n + (size_t)(a0 + j) * n + jd0 + jl;
+              dpre[j] = dataf[pix];
+              wpre[j] = wgtf[pix];
+            }
+          };
+          // row pass (x taps) fused with the column down-sampling, lane = high-res row: as in the loop below
+          auto row_request = [&](int task, int bqx) {
+            const int s = g0 + task / NBLK, jd0 = (task % NBLK) * JB;
+            const float *tx = TAPS + (s * 4 + 0) * NTP;
+#pragma unroll
+            for (int h = 0; h < NP; ++h) tr2[h] = (lc_v2f){tx[NT - 1 - 2 * h], tx[NT - 2 - 2 * h]};  // tx[-1] = 0
+            const float *trow = T + lane * TSA + AP + SS * (jd0 - bqx) - (NT - 1);
+#pragma unroll
+            for (int i = 0; i < WL2; ++i) win2[i] = (lc_v2f){trow[2 * i], trow[2 * i + 1]};
+          };
+          auto row_fma_store = [&] {
+            lc_v2f acc[JB];
+#pragma unroll
+            for (int j = 0; j < JB; ++j) acc[j] = (lc_v2f){0.f, 0.f};
+#pragma unroll
+            for (int h = 0; h < NP; ++h) {
+#pragma unroll
+              for (int j = 0; j < JB; ++j) acc[j] = pk_fma(tr2[h], win2[j + h], acc[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < JB; ++j) R2w[j * TSA + lane] = acc[j].x + acc[j].y;
+          };
+          // transposed column pass, lane = (column, strip of high-res rows): as in the loop below
+          auto tcol_request = [&](int task, int bqy) {
+            const float *ty = TAPS + ((g0 + task / NBLK) * 4 + 2) * NTP;
+#pragma unroll
+            for (int q = 0; q < NP; ++q) py[q] = (lc_v2f){ty[2 * q], ty[2 * q - 1]};  // ty[-1] = ty[NT] = 0
+            const float *rcol = RESw + (bqy + a0) * C::JBP + jl;
+#pragma unroll
+            for (int i = 0; i < WI; ++i) rv[i] = rcol[i * C::JBP];
+          };
+          auto tcol_fma_store = [&](int task) {
+            const int sl = task / NBLK, jd0 = (task % NBLK) * JB;
+            lc_v2f out2[LA];
+#pragma unroll
+            for (int h = 0; h < LA; ++h) out2[h] = (lc_v2f){0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < WI; ++i) {
+              const lc_v2f rr = pk_bcast(rv[i]);
+#pragma unroll
+              for (int h = 0; h < LA; ++h)
+                if (i - h >= 0 && i - h < NP) out2[h] = pk_fma(py[i - h], rr, out2[h]);
+            }
+            float *vrow = V + (sl * N + SS * a0) * C::VS + C::VO + jd0 + jl;
+#pragma unroll
+            for (int h = 0; h < LA; ++h) {
+              vrow[(2 * h) * C::VS] = out2[h].x;
+              vrow[(2 * h + 1) * C::VS] = out2[h].y;
+            }
+            if constexpr (!V_ZERO_ONCE) {
+              if (jd0 + jl == 0) {
+#pragma unroll
+                for (int r = 0; r < SS * LA; ++r) V[(sl * N + SS * a0 + r) * C::VS] = 0.f;
+              }
+              if (jd0 + jl == n - 1) {
+#pragma unroll
+                for (int r = 0; r < SS * LA; ++r) V[(sl * N + SS * a0 + r) * C::VS + n + 1] = 0.f;
+              }
+            }
+          };
+          // kdone: tasks this wave has finished - the wave that is behind gets the issue priority.  (The task index is the same in
+          // every lane; said so, the loop's branches and the tasks' star and block indices are scalar.)
+          int task = __builtin_amdgcn_readfirstlane(wid), kdone = 0;
+          int bqy = 0;
+          if (task < ntask) {
+            progress_prio(0);
+            pixel_request(task);
+            LC_STAMP(10);
+            row_request(task, BQ[(g0 + task / NBLK) * 2 + 0]);
+            bqy = BQ[(g0 + task / NBLK) * 2 + 1];
+            row_fma_store();
+            wave_lds_sync();
+          }
+#pragma clang loop unroll(disable)
+          for (; task < ntask; task += C::NW, ++kdone) {
+            progress_prio(kdone);
+            LC_STAMP(11);
+            const int sl = task / NBLK, blk = task % NBLK, s = g0 + sl, jd0 = blk * JB;
+            const bool more = task + C::NW < ntask;  // wave-uniform
+            // (the window bases of the next task, x for its row pass and y for its column pass: read a task ahead so that the
+            //  address chains start from registers; at a star index that exists when there is no next task)
+            const int snext = min(g0 + (task + C::NW) / NBLK, S - 1);
+            const int bqx_next = BQ[snext * 2 + 0], bqy_next = BQ[snext * 2 + 1];
+            const float amp = SP[s * 4 + 0], sky = SP[s * 4 + 3];
+            // column pass (y taps) fused with the row down-sampling, residuals, reductions: as in the loop below
+            float chi = 0.f, ga = 0.f, gy = 0.f, gs = 0.f;
+            {
+              lc_v2f tyd[NT];
+#pragma unroll
+              for (int k = 0; k < NT; ++k) tyd[k] = TAPP[(s * 2 + 1) * NT + k];
+              float win[WL];
+              const float *r2 = R2w + jl * TSA + SS * (a0 - bqy) - (NT - 1);
+#pragma unroll
+              for (int i = 0; i < WL; ++i) win[i] = r2[i];
+              float lgy = 0.f;
+              lc_v2f fvys[LC];
+#pragma unroll
+              for (int j = 0; j < LC; ++j) fvys[j] = (lc_v2f){0.f, 0.f};
+#pragma unroll
+              for (int k = 0; k < NT; ++k) {
+#pragma unroll
+                for (int j = 0; j < LC; ++j) fvys[j] = pk_fma(tyd[k], pk_bcast(win[SS * j - k + NT - 1]), fvys[j]);
+                asm volatile("" : "+v"(fvys[0]), "+v"(fvys[1]), "+v"(fvys[2]), "+v"(fvys[3]));  // (LC independent chains, as below)
+              }
+#pragma unroll
+              for (int j = 0; j < LC; ++j) {
+                const float fv = fvys[j].x, fy = fvys[j].y;
+                const float model = fmaf(amp, fv, sky);
+                const float res = model - dpre[j];
+                const float rw = wpre[j] * res;
+                chi = fmaf(rw, res, chi);
+                ga = fmaf(rw, fv, ga);
+                lgy = fmaf(rw, fy, lgy);
+                gs += rw;
+                RESw[(a0 + j) * C::JBP + jl] = rw;
+                if (A.out_model) A.out_model[(size_t)f * S * n * n + (size_t)s * n * n + (size_t)(a0 + j) * n + jd0 + jl] = model;
+              }
+              gy += lgy * amp * SS;
+            }
+            wave_sum4(chi, ga, gy, gs);
+            if (lane == 0) {
+              float *r = RED + (s * NBLK + blk) * 5;
+              r[0] = chi;
+              r[1] = ga;
+              r[3] = gy;
+              r[4] = gs;
+            }
+            wave_lds_sync();
+            LC_STAMP(12);
+            if (more) {
+              // Every read of both streams is requested in front of the first multiply-add, pinned where it stands (the scheduler
+              // otherwise sinks the second stream's reads behind the first stream's arithmetic, to save registers): the row pass
+              // first, its 56 multiply-adds cover the transposed pass's round trip.
+              LC_STAMP(19);
+              pixel_request(task + C::NW);
+              row_request(task + C::NW, bqx_next);
+              tcol_request(task, bqy);
+              __builtin_amdgcn_sched_barrier(0);
+              row_fma_store();
+              tcol_fma_store(task);
+              wave_lds_sync();  // R2w of the next task complete; RESw may be rewritten
+              LC_STAMP(18);
+            } else {
+              tcol_request(task, bqy);
+              tcol_fma_store(task);
+              wave_lds_sync();
+              LC_STAMP(13);
+            }
+            bqy = bqy_next;
+          }
+        } else {
         int kdone = 0;  // tasks this wave has finished: the wave that is behind gets the issue priority (progress_prio)
         for (int task = wid; task < SG * NBLK; task += C::NW, ++kdone) {
           progress_prio(kdone);
@@ -646,14 +855,17 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
                     vrow[(2 * h) * C::VS] = out2[h].x;
                     vrow[(2 * h + 1) * C::VS] = out2[h].y;
                   }
-                  // the zero columns (the starlet phase reuses this region, so they are rewritten every iteration)
-                  if (jd0 + jl == 0) {
+                  // the zero columns (the starlet phase reuses this region, so they are rewritten every iteration;
+                  // V_ZERO_ONCE: no starlet in this workgroup, written in front of the iteration loop)
+                  if constexpr (!V_ZERO_ONCE) {
+                    if (jd0 + jl == 0) {
 #pragma unroll
-                    for (int r = 0; r < SS * LA; ++r) V[(sl * N + SS * a0 + r) * C::VS] = 0.f;
-                  }
-                  if (jd0 + jl == n - 1) {
+                      for (int r = 0; r < SS * LA; ++r) V[(sl * N + SS * a0 + r) * C::VS] = 0.f;
+                    }
+                    if (jd0 + jl == n - 1) {
 #pragma unroll
-                    for (int r = 0; r < SS * LA; ++r) V[(sl * N + SS * a0 + r) * C::VS + n + 1] = 0.f;
+                      for (int r = 0; r < SS * LA; ++r) V[(sl * N + SS * a0 + r) * C::VS + n + 1] = 0.f;
+                    }
                   }
                 }
               }
@@ -696,6 +908,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           wave_lds_sync();  // the scratch is rewritten by the wave's next task
           LC_STAMP(13);
         }
+        }  // !TASK_AHEAD
         __builtin_amdgcn_s_setprio(0);
         LC_STAMP(14);
 #ifdef LC_STAMPS

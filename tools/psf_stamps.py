@@ -4,7 +4,7 @@ import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lightcurver_amd import _lib
-_lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), 'liblcmi_dbg.so')
+_lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), os.environ.get('LCMI_DBG_LIB', 'liblcmi_dbg.so'))
 from lightcurver_amd.psf_batch import PsfBatch
 from lightcurver_amd.synthetic import make_psf_dataset
 cfg = dict(F=100, S=8, n=int(sys.argv[1]) if len(sys.argv) > 1 else 32, ss=2, seed=1)
@@ -44,7 +44,15 @@ for blk, label in ((0, 'block 0 (role 0 / single form)'), (64, 'block 8 (role 1)
         print(f'  {trim.get(k, names[k]):34s} {s[k]-prev:8d} ticks  {100*(s[k]-prev)/tot:5.1f}%')
         prev = s[k]
     fine = {10: 'task start (prefetch issued)', 11: 'row pass', 12: 'column pass + reductions', 13: 'transposed column pass', 14: 'wave 0 done with its tasks', 15: 'barrier (other waves)', 16: 'per-star sums', 17: 'P5 transposed row pass'}
-    if s[10]:
+    if s[10] and s[18]:
+        # C2 two-workgroup kernel with TASK_AHEAD (csrc/psf_kernels.h): stamp 10 precedes the row pass in front of the loop, 11 is
+        # the top of the last task, 19 / 18 enclose the last stretch of transposed pass + next task's row pass (third task)
+        print('   last group, wave 0 (pipelined tasks):')
+        print(f"     {'3rd task: transposed + next row pass':34s} {s[18]-s[19]:8d} ticks")
+        print(f"     {'first row pass .. top of last task':34s} {s[11]-s[10]:8d} ticks")
+        for a in range(12, 18):
+            print(f'     {fine[a]:34s} {s[a]-s[a-1]:8d} ticks')
+    elif s[10]:
         print('   last group, wave 0, last task:')
         for a in range(11, 18):
             print(f'     {fine[a]:34s} {s[a]-s[a-1]:8d} ticks')

@@ -43,7 +43,9 @@ def calibrated_light_curves(star_stacks, roi_stack, subsampling_factor, xs_pixel
     """star_stacks: per reference star (data, noisemap, psf) = (E_g, n, n), (E_g, n, n), (E_g, n ss, n ss), cleaned
     (``star_photometry.prepare_star_epochs``), in the units of the frames; copied, so the caller's arrays stay as they are.
     roi_stack: (data, noisemap, cosmics_mask, narrow_psf) of the ROI over ALL ``n_frames`` frames, same units.
-    xs_pixels, ys_pixels: the point sources of the ROI (pixels of the first kept frame).  star_frame_index: per star the
+    xs_pixels, ys_pixels: the point sources of the ROI, (M,) in pixels of the first kept frame's stamp, or (n_frames, M):
+    row j in pixels of frame j's stamp, of which row ``kept[0]`` is used (which frame comes first is decided here, by the
+    selection and ``mjd``).  star_frame_index: per star the
     frame of each of its epochs (every star keeps its own frame selection).  catalog_mags (S,): calibrated magnitudes of
     the stars, for the zero-point.  mjd (n_frames,): orders the kept frames.  angles_to_north (n_frames,).
 
@@ -59,6 +61,12 @@ def calibrated_light_curves(star_stacks, roi_stack, subsampling_factor, xs_pixel
     star_results, star_fluxes, star_d_fluxes, star_chi2 (S, n_frames), fluxes_chi2_bounds, psf_chi2_bounds, normalization
     (the dict of ``calculate_coefficients``), zeropoint, zeropoint_uncertainty (n_frames,) or None, prepared (the dict of
     ``prepare_roi_cutouts``), roi_fit (of ``model_roi_cutouts``), light_curves (of ``fluxes_from_model``)."""
+    per_frame_positions = np.ndim(xs_pixels) == 2 or np.ndim(ys_pixels) == 2
+    if per_frame_positions:
+        xs_pixels, ys_pixels = (np.asarray(v, dtype=np.float64) for v in (xs_pixels, ys_pixels))
+        if xs_pixels.ndim != 2 or xs_pixels.shape != ys_pixels.shape or xs_pixels.shape[0] != int(n_frames):
+            raise ValueError(f'per-frame positions must both be (n_frames, M) with n_frames = {int(n_frames)}, got '
+                             f'{xs_pixels.shape} and {ys_pixels.shape}')
     stacks = [tuple(np.array(a, dtype=np.float64) for a in stack) for stack in star_stacks]
     star_results = do_many_stars_forward_modelling(stacks, subsampling_factor, n_iter=star_n_iter,
                                                    uniform_background_per_epoch=uniform_background_per_epoch,
@@ -80,6 +88,8 @@ def calibrated_light_curves(star_stacks, roi_stack, subsampling_factor, xs_pixel
                                    roi_xy=roi_xy, frame_shape=frame_shape, ctx=ctx)
     kept = prepared['kept']
     angles = None if angles_to_north is None else np.asarray(angles_to_north, dtype=np.float64)[kept]
+    if per_frame_positions:      # the fit takes the sources where they are in its first epoch
+        xs_pixels, ys_pixels = xs_pixels[kept[0]], ys_pixels[kept[0]]
     roi_fit = model_roi_cutouts(prepared['data'], prepared['noisemap'], prepared['psf'], subsampling_factor, xs_pixels,
                                 ys_pixels, angles_to_north=angles, **roi_fit_options)
     n_sources = np.atleast_1d(np.asarray(xs_pixels)).size

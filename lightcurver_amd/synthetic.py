@@ -161,6 +161,122 @@ def make_roi_dataset(E, M, n, ss=2, seed=0, rms=5.0, with_background=True, shift
                 psf=psf.astype(dtype), ss=ss, scale=scale, truth=truth)
 
 
+def _narrow_psf_of_seeing(rng, N, ss, fwhm_full, perturb=0.02):
+    """``make_narrow_psf`` with the full-resolution FWHM given instead of drawn (data pixels): (psf, parameters)."""
+    q = rng.uniform(0.9, 1.0)
+    phi = rng.uniform(0.0, math.pi)
+    fwhm = math.sqrt(max(fwhm_full ** 2 - (GAUSS_FWHM / ss) ** 2, 1.0))
+    mof = _moffat(N, ss, fwhm, fwhm * q, phi, 3.0)
+    pert = gaussian_filter(rng.standard_normal((N, N)), 2.0)
+    pert *= perturb * mof.max() / np.abs(pert).max()
+    pert *= mof / mof.max() * 4.0
+    s = mof + pert
+    return s / s.sum(), dict(fwhm_x=fwhm, fwhm_y=fwhm * q, phi=phi, beta=3.0, fwhm_full=fwhm_full)
+
+
+def similarity_matrix(rotation_deg, shift_xy, frame_shape, scale=1.0):
+    """The 3 x 3 matrix (reference pixels -> frame pixels, (x, y), as ``plate_solving.register_frames`` returns them) of a
+    rotation by ``rotation_deg`` about the frame's centre ((w-1)/2, (h-1)/2) followed by ``shift_xy``."""
+    h, w = frame_shape
+    c = np.array([(w - 1) / 2.0, (h - 1) / 2.0])
+    th = math.radians(rotation_deg)
+    lin = scale * np.array([[math.cos(th), -math.sin(th)], [math.sin(th), math.cos(th)]])
+    m = np.eye(3)
+    m[:2, :2] = lin
+    m[:2, 2] = c - lin @ c + np.asarray(shift_xy, np.float64)
+    return m
+
+
+def make_frames(frame_shape, stars_xy, star_fluxes, roi_sources_xy, roi_fluxes, rotations_deg, shifts_xy, seeing_pixels,
+                transparency, sky_levels, exptimes, ss=2, psf_size=16, rms_electrons=10.0, blank_frames=(), seed=0,
+                good_frames=None, footprint_margin=None, min_good_stars=6, min_peak_to_noise=50.0, dtype=np.float32):
+    """K whole frames of one field, in electrons per second and NOT sky-subtracted, with the truth that made them: the
+    scene of the tests of ``pipeline.light_curves_from_frames``.
+
+    frame_shape (h, w).  stars_xy (S, 2), roi_sources_xy (M, 2): (x, y) in pixels of the reference frame, which is the
+    frame whose rotation and shift are zero.  star_fluxes (S,), roi_fluxes (K, M): electrons per second at transparency 1.
+    Per frame: rotations_deg and shifts_xy (K, 2) (``similarity_matrix``: reference pixels -> the frame's), seeing_pixels
+    (FWHM of the full PSF), transparency (multiplies every source), sky_levels (electrons per second, constant over the
+    frame) and exptimes (seconds).  ``blank_frames``: frames that hold sky and noise only.
+
+    Every source is rendered with its frame's PSF, built as the stamp generators of this file build theirs: a narrow PSF
+    on an (ss psf_size)^2 grid, convolved with the Gaussian of FWHM 2 high-resolution pixels placed at the source's
+    position, binned by ss.  A source therefore has no light beyond psf_size / 2 pixels.  The noise is Gaussian with the
+    variance that the noise map of ``FrameSet.cut_stamps`` assumes: per pixel, in electrons, ``rms_electrons``^2 + the
+    sources' electrons; ``rms_electrons / exptime`` is the background rms of the frame in its own units.
+
+    Returns dict: frames (K, h, w), exptimes (K,), truth = dict(transforms (K, 3, 3), stars_xy (K, S, 2) and roi_xy
+    (K, M, 2): the positions in every frame, star_fluxes (K, S) and roi_fluxes (K, M): electrons per second in the frame
+    (transparency included), narrow_psf (K, ss psf_size, ss psf_size), transparency, seeing_pixels, background_rms (K,),
+    stars_in_frames (K, S) where ``footprint_margin`` is given).
+
+    Asserted here, on the host in float64, so that tests can rely on it: with ``footprint_margin`` and ``good_frames``
+    given, every good frame holds at least ``min_good_stars`` stars inside its footprint shrunk by the margin
+    (``utilities.footprint.points_in_footprints``), and no star lies within 1 pixel of a shrunk footprint's boundary in
+    any frame with sources (the stars-in-frames table then cannot hinge on registration noise); every star that is in a
+    frame's table peaks above ``min_peak_to_noise`` times the noise of a sky pixel of that frame."""
+    from .utilities.footprint import frame_footprints, points_in_footprints
+    rng = np.random.default_rng(seed)
+    h, w = (int(v) for v in frame_shape)
+    stars_xy = np.asarray(stars_xy, np.float64).reshape(-1, 2)
+    roi_sources_xy = np.asarray(roi_sources_xy, np.float64).reshape(-1, 2)
+    S, M = len(stars_xy), len(roi_sources_xy)
+    K = len(rotations_deg)
+    star_fluxes = np.asarray(star_fluxes, np.float64).reshape(S)
+    roi_fluxes = np.asarray(roi_fluxes, np.float64).reshape(K, M)
+    per_frame = [np.asarray(v, np.float64).reshape(-1) for v in (seeing_pixels, transparency, sky_levels, exptimes)]
+    shifts_xy = np.asarray(shifts_xy, np.float64).reshape(-1, 2)
+    if any(len(v) != K for v in per_frame) or len(shifts_xy) != K:
+        raise ValueError(f'one rotation, shift, seeing, transparency, sky level and exposure time per frame ({K})')
+    seeing, transparency, sky, t = per_frame
+    blank = set(int(k) for k in blank_frames)
+    N = ss * int(psf_size)
+    pad = 2                                                   # the Gaussian's own reach beyond the narrow PSF's support
+    pn = int(psf_size) + 2 * pad
+    P = ss * pn
+    transforms = np.stack([similarity_matrix(rotations_deg[k], shifts_xy[k], (h, w)) for k in range(K)])
+    sources_ref = np.concatenate([stars_xy, roi_sources_xy])
+    positions = np.stack([sources_ref @ transforms[k][:2, :2].T + transforms[k][:2, 2] for k in range(K)])   # (K, S + M, 2)
+    fluxes = np.concatenate([np.broadcast_to(star_fluxes, (K, S)), roi_fluxes], axis=1) * transparency[:, None]
+    narrow = np.zeros((K, N, N))
+    frames = np.zeros((K, h, w))
+    peaks = np.zeros((K, S + M))
+    for k in range(K):
+        narrow[k], _ = _narrow_psf_of_seeing(rng, N, ss, float(seeing[k]))
+        clean = np.zeros((h, w))
+        if k not in blank:
+            for i, (x, y) in enumerate(positions[k]):
+                x0, y0 = int(round(x)) - pn // 2, int(round(y)) - pn // 2        # the patch covers [x0, x0 + pn)
+                if x0 >= w or y0 >= h or x0 + pn <= 0 or y0 + pn <= 0:
+                    continue
+                # high-resolution index of data coordinate u: ss (u - x0) + (ss - 1) / 2
+                g = _gauss2d(P, ss * (x - x0) + (ss - 1) / 2.0, ss * (y - y0) + (ss - 1) / 2.0)
+                stamp = fluxes[k, i] * _blocksum(fftconvolve(g, narrow[k], mode='same'), ss)
+                peaks[k, i] = stamp.max()
+                xs, xe, ys, ye = max(x0, 0), min(x0 + pn, w), max(y0, 0), min(y0 + pn, h)
+                clean[ys:ye, xs:xe] += stamp[ys - y0:ye - y0, xs - x0:xe - x0]
+        sigma = np.sqrt(rms_electrons ** 2 + np.abs(clean) * t[k]) / t[k]
+        frames[k] = sky[k] + clean + sigma * rng.standard_normal((h, w))
+    truth = dict(transforms=transforms, stars_xy=positions[:, :S], roi_xy=positions[:, S:], star_fluxes=fluxes[:, :S],
+                 roi_fluxes=fluxes[:, S:], narrow_psf=narrow, transparency=transparency, seeing_pixels=seeing,
+                 background_rms=rms_electrons / t)
+    if footprint_margin is not None:
+        footprints = frame_footprints(list(transforms), (h, w))
+        table = points_in_footprints(stars_xy, footprints, footprint_margin)
+        truth['stars_in_frames'] = table
+        with_sources = [k for k in range(K) if k not in blank]
+        for sign in (-1.0, 1.0):
+            moved = points_in_footprints(stars_xy, footprints, max(footprint_margin + sign, 0.0))
+            assert np.array_equal(moved[with_sources], table[with_sources]), \
+                'a star within 1 pixel of the boundary of a shrunk footprint'
+        for k in (good_frames if good_frames is not None else ()):
+            assert table[k].sum() >= min_good_stars, f'frame {k}: {table[k].sum()} stars inside its shrunk footprint'
+        for k in with_sources:
+            ratio = peaks[k, :S][table[k]] * t[k] / rms_electrons
+            assert np.all(ratio > min_peak_to_noise), f'frame {k}: a star peaks at {ratio.min():.1f} x the sky noise'
+    return dict(frames=frames.astype(dtype), exptimes=t, truth=truth)
+
+
 def make_config(name, **overrides):
     cfg = dict(CONFIGS[name])
     cfg.update(overrides)

@@ -387,6 +387,40 @@ int lc_frames_aperture_sums(lc_frames *f, int P, const int32_t *frame /*[P]*/, c
                             int with_error, double *sum, double *sum_err /*nullable*/, double *area /*nullable*/,
                             double *bad_area /*nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- co-addition of the registered frames of a set: the deep image of the field -------------------------------------
+ * DESIGN.md section 5 "Co-addition of frames" is the SPEC; csrc/coadd.hip.  n frames of the set (frame[k], in any order,
+ * repeated at will) are resampled onto a grid of H x W reference pixels whose pixel (i, j) is the reference pixel
+ * (x0 + j, y0 + i), and combined per pixel.  affine[k] = a, b, c, d, e, f maps reference pixels to the pixels of frame k:
+ * x' = (a x + b y) + c, y' = (d x + e y) + f, in double (the rows of lc_register_sources' transform, and of
+ * SimilarityTransform.params[:2]).  order 1: bilinear; order 3: Keys' cubic convolution with a = -1/2, no prefilter.  A
+ * sample is missing (NaN) unless every tap lies inside the frame; NaN taps propagate.  A sample is multiplied by
+ * float32(flux_scale[k] |det affine[k]|), which keeps flux per reference pixel.  combine, over the finite samples of a
+ * pixel in the order of the list, with the per-frame weight[k] where lc_align_stack has 1 / noise:
+ *   LC_COADD_MEAN        sum w v / sum w
+ *   LC_COADD_MEDIAN      the middle order statistic, 0.5 (lo + hi) for an even count; weights enter weight_out only
+ *   LC_COADD_SIGMA_CLIP  median, population deviation, keep |v - median| <= n_sigma deviation, weighted mean of the kept
+ * Outputs [H][W]: image; weight_out = sum of weight[k] over the kept samples; count = the kept samples; n_rejected.  A
+ * pixel without a sample gives NaN, 0, 0, 0.  The results do not depend on scratch_rows, and a frame's samples do not
+ * depend on what else is in the list, bit for bit.  Works on a raw or an imported set and leaves the planes unchanged.
+ * Device memory beyond the set: the four outputs and n scratch_rows W samples.  kernel_ms = device time of all kernels.
+ *   Checked on the host before anything is launched, the outputs untouched, LC_ERR_INVALID: n < 1, a missing frame,
+ *   affine, cfg or image, a frame index outside [0, K), an affine entry that is not finite or det = 0, a flux scale that
+ *   is not finite, a weight that is negative or not finite, H or W < 1, H W >= 2^31, an order other than 1 or 3, an
+ *   unknown combine, n_sigma <= 0 or not finite, scratch_rows < 0. */
+#define LC_COADD_MEAN 0
+#define LC_COADD_MEDIAN 1
+#define LC_COADD_SIGMA_CLIP 2
+typedef struct {
+  int32_t order;        /* 1 or 3 */
+  int32_t combine;      /* LC_COADD_* */
+  float n_sigma;        /* read by every combine: > 0 and finite */
+  int32_t scratch_rows; /* output rows resampled per strip; 0: as many as fit a budget of 128 MiB */
+} lc_coadd_cfg;
+int lc_frames_coadd(lc_frames *f, int n, const int32_t *frame /*[n]*/, const double *affine /*[n][6]*/,
+                    const float *flux_scale /*[n], nullable: 1*/, const float *weight /*[n], nullable: 1*/, int H, int W,
+                    int x0, int y0, const lc_coadd_cfg *cfg, float *image /*[H][W]*/, float *weight_out /*nullable*/,
+                    int32_t *count /*nullable*/, int32_t *n_rejected /*nullable*/, float *kernel_ms /*nullable*/);
+
 /* ---- registration of source lists by star triangles (astroalign.find_transform), batched ----------------------------------
  * The reference gives a frame its WCS from another frame's, or from Gaia positions, with one astroalign.find_transform per
  * frame (lightcurver/processes/alternate_plate_solving_adapt_existing_wcs.py:24, alternate_plate_solving_with_gaia.py:66).

@@ -60,6 +60,13 @@ class StackCfg(C.Structure):
     _fields_ = [('n_sigma', C.c_float), ('clip', C.c_int32)]
 
 
+class CoaddCfg(C.Structure):
+    _fields_ = [('order', C.c_int32), ('combine', C.c_int32), ('n_sigma', C.c_float), ('scratch_rows', C.c_int32)]
+
+
+COADD_COMBINE = {'mean': 0, 'median': 1, 'sigma_clip': 2}   # LC_COADD_* of include/lcmi.h
+
+
 class BackgroundCfg(C.Structure):
     _fields_ = [('bw', C.c_int32), ('bh', C.c_int32), ('fw', C.c_int32), ('fh', C.c_int32), ('fthresh', C.c_float)]
 
@@ -163,6 +170,8 @@ SIGNATURES = {
     'lc_aperture_sums': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_uint8), C.c_int, ip, dp, dp, dp, dp,
                                    dp, dp, C.POINTER(C.c_float)]),
     'lc_frames_aperture_sums': (C.c_int, [vp, C.c_int, ip, dp, dp, fp, fp, C.c_int, dp, dp, dp, dp, C.POINTER(C.c_float)]),
+    'lc_frames_coadd': (C.c_int, [vp, C.c_int, ip, dp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CoaddCfg), fp, fp,
+                                  ip, ip, C.POINTER(C.c_float)]),
     'lc_register_supported': (C.c_int, [C.c_int]),
     'lc_register_sources': (C.c_int, [vp, C.c_int, C.c_int, dp, ip, dp, ip, C.POINTER(RegisterCfg), dp, ip, ip, ip, ip,
                                       C.POINTER(C.c_float)]),

@@ -74,6 +74,8 @@ class FrameSet:
 
         out = _import(call, self.shape, exptimes, n_boxes, mask_sources_first, detection_threshold, min_area,
                       max_objects, False, bool(download_sub), deblend)
+        if self.imported:
+            self._globalrms = np.array(out['globalrms'], np.float32)      # what ``coadd`` weighs the frames with
         if not download_sub:
             del out['sub']
         return out
@@ -154,6 +156,62 @@ class FrameSet:
             handle, P, frame.ctypes.data_as(_i32p), dptr(xy), dptr(rr), ptr(t), ptr(rms), int(bool(with_error)),
             dptr(out['sum']), dptr(out['sum_err']), dptr(out['area']), dptr(out['bad_area']), C.byref(ms)),
             'lc_frames_aperture_sums')
+        out['kernel_ms'] = ms.value
+        return out
+
+    def coadd(self, frame_index, transforms, shape=None, origin=(0, 0), flux_scale=None, weights=None, order=3,
+              combine='sigma_clip', n_sigma=3.0, scratch_rows=0):
+        """The frames ``frame_index`` (any order, repeated at will) resampled onto one grid of reference pixels and
+        combined per pixel, in one device call (``lc_frames_coadd``; DESIGN.md section 5 "Co-addition of frames").
+        transforms: per frame a ``SimilarityTransform`` as ``register_frames`` gives it, a (2, 3) or a (3, 3) array: it
+        maps reference pixels (x, y) to the frame's.  shape (H, W) and origin (x0, y0): the grid, by default the frame's
+        own.  flux_scale: per frame, the sample is multiplied by it and by |det| of the transform (default 1).  weights:
+        per frame, >= 0; by default, after ``import_frames``, 1 / (s rms)^2 with s the factor above and rms the recorded
+        ``globalrms``, otherwise 1.  order 1 (bilinear) or 3 (Keys' cubic convolution); combine 'mean', 'median' or
+        'sigma_clip' at ``n_sigma``.  ``scratch_rows``: output rows resampled per strip (0: from a budget); the result
+        does not depend on it.  Returns dict(image float32 (H, W), NaN where no frame has a sample; weight float32, the sum
+        of the weights of the kept samples; count, n_rejected int32; kernel_ms).  The planes stay as they are."""
+        handle = self._handle()
+        K, h, w = self.shape
+        frame = np.ascontiguousarray(np.asarray(frame_index, np.int32).reshape(-1))
+        n = len(frame)
+        if n < 1:
+            raise ValueError('coadd: no frame')
+        if ((frame < 0) | (frame >= K)).any():
+            raise ValueError(f'coadd: a frame index outside 0 .. {K - 1}')
+        if hasattr(transforms, 'params') or (isinstance(transforms, np.ndarray) and transforms.ndim == 2):
+            transforms = [transforms]
+        if len(transforms) != n:
+            raise ValueError(f'coadd: {n} frames but {len(transforms)} transforms')
+        affine = np.empty((n, 6), np.float64)
+        for k, t in enumerate(transforms):
+            m = np.asarray(t.params if hasattr(t, 'params') else t, np.float64)
+            if m.shape not in ((2, 3), (3, 3)):
+                raise ValueError(f'coadd: a transform of shape {m.shape}, not (2, 3) or (3, 3)')
+            affine[k] = m[:2].reshape(6)
+        if combine not in _lib.COADD_COMBINE:
+            raise ValueError(f'coadd: combine must be one of {tuple(_lib.COADD_COMBINE)}, not {combine!r}')
+        H, W = (h, w) if shape is None else (int(shape[0]), int(shape[1]))
+        x0, y0 = int(origin[0]), int(origin[1])
+        if H < 1 or W < 1 or H * W >= 2 ** 31:
+            raise ValueError(f'coadd: a grid of {H} x {W} pixels')
+        per_slot = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32).reshape(-1), (n,)), np.float32)
+        g = None if flux_scale is None else per_slot(flux_scale)
+        if weights is None and self.imported:
+            rms = self._globalrms[frame].astype(np.float64)
+            det = np.abs(affine[:, 0] * affine[:, 4] - affine[:, 1] * affine[:, 3])
+            s = (1.0 if g is None else g.astype(np.float64)) * det
+            with np.errstate(all='ignore'):
+                weights = 1.0 / (s * rms) ** 2
+        wt = None if weights is None else per_slot(weights)
+        cfg = _lib.CoaddCfg(int(order), _lib.COADD_COMBINE[combine], float(n_sigma), int(scratch_rows))
+        out = dict(image=np.empty((H, W), np.float32), weight=np.empty((H, W), np.float32),
+                   count=np.empty((H, W), np.int32), n_rejected=np.empty((H, W), np.int32))
+        ms = C.c_float()
+        self.ctx.check(self._l.lc_frames_coadd(
+            handle, n, frame.ctypes.data_as(_i32p), affine.ctypes.data_as(_lib.dp), ptr(g), ptr(wt), H, W, x0, y0,
+            C.byref(cfg), ptr(out['image']), ptr(out['weight']), out['count'].ctypes.data_as(_i32p),
+            out['n_rejected'].ctypes.data_as(_i32p), C.byref(ms)), 'lc_frames_coadd')
         out['kernel_ms'] = ms.value
         return out
 

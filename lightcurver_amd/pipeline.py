@@ -63,7 +63,8 @@ def light_curves_from_frames(frames, exptimes, roi_xy, point_sources_xy, *, refe
                              constraints_on_frame_columns_for_roi=None, constraints_on_normalization_coeff=None,
                              fix_point_source_astrometry=False, starting_background=None, further_optimize_background=True,
                              roi_model_regularization=None, roi_deconv_translations_iters=300, roi_deconv_all_iters=2000,
-                             max_scale_deviation=0.02, import_options=None, ctx=None):
+                             max_scale_deviation=0.02, import_options=None, star_catalogue_from='reference',
+                             coadd_order=3, coadd_combine=None, ctx=None):
     """frames: a (K, h, w) array in electrons per second, NOT sky-subtracted, or a ``FrameSet`` that has not been imported
     (it is imported here and stays open; an array is uploaded to a set of its own, closed on return).  exptimes: one per
     frame, or one for all.  roi_xy (2,) and point_sources_xy (M, 2): pixel positions (x, y) in frame ``reference``,
@@ -75,6 +76,13 @@ def light_curves_from_frames(frames, exptimes, roi_xy, point_sources_xy, *, refe
       flux, distance_to_roi; reference pixels), for a caller who has a real catalogue; by default it is built from the
       reference frame's own sources, those within ``roi_exclusion_radius`` pixels of the ROI dropped (default: half the
       ROI stamp).  ``catalog_mags``: one calibrated magnitude per star of ``star_catalogue``, which it therefore needs.
+    * ``star_catalogue_from``: where the catalogue comes from when ``star_catalogue`` is None.  'reference': the sources
+      of the reference frame, as above.  'coadd': the sources of the co-add of the frames that pass stage 3
+      (``processes.coaddition.coadd_frames`` on the reference frame's grid with ``relative_flux_scales`` and the weights
+      1 / (scale rms)^2, interpolation ``coadd_order``; ``coadd_combine`` None means 'median' below 11 frames, where the
+      deviation of so few samples says little, and 'sigma_clip' from 11 on), extracted with ``extract_stars`` at the variance
+      1 / weight: deeper than one frame by about the root of their number, without cosmic rays, and not tied to what
+      the reference frame happened to detect.  The co-add is returned as ``coadd`` and timed as ``seconds['coadd']``.
     * ``star_selection_strategy``: 'stars_per_frame' (every frame uses the stars inside its own footprint) or
       'common_footprint_stars' (only stars that are in every surviving frame).  ``footprint_margin``: pixels a star must
       keep from a frame's edge (``points_in_footprints``; the reference's 4 arcseconds; default: half the star stamp).
@@ -101,7 +109,7 @@ def light_curves_from_frames(frames, exptimes, roi_xy, point_sources_xy, *, refe
     normalisation star, frames in the caller's numbering), sources_tables, psf_results (K, None where there is none),
     psf_chi2 (K,), seeing_pixels (K,), ellipticity (K,), background_rms (K,), angles (K,) degrees, scales (K,), roi_origin
     (K, 2) int (x0, y0) of the ROI stamps (-1 where none was cut), point_sources_in_stamps (K, M, 2), seconds {stage: wall
-    clock}.
+    clock}; with the catalogue taken from the co-add also coadd: the dict of ``coadd_frames`` plus its ``sources_table``.
 
     ValueError, before anything runs on the device, for shapes that do not match, a frame set that was imported already,
     fewer than 3 frames, a ROI outside the reference frame, and a stamp size no kernel or embedding takes; and as soon as
@@ -114,11 +122,12 @@ def light_curves_from_frames(frames, exptimes, roi_xy, point_sources_xy, *, refe
     from . import sep
     from .frames import FrameSet
     from .processes.calibration import calibrated_light_curves
+    from .processes.coaddition import coadd_frames, relative_flux_scales
     from .processes.cutout_making import cutout_origin, extract_all_stamps_of_frames
     from .processes.frame_characterization import estimate_seeing
     from .processes.plate_solving import positions_in_frames, register_frames
     from .processes.psf_modelling import model_psfs_of_frames
-    from .processes.star_extraction import sources_table_from_objects
+    from .processes.star_extraction import extract_stars, sources_table_from_objects
     from .processes.star_photometry import prepare_star_epochs
     from .processes.star_selection import reference_star_catalogue, select_stars
 
@@ -167,6 +176,12 @@ def light_curves_from_frames(frames, exptimes, roi_xy, point_sources_xy, *, refe
         raise ValueError('catalog_mags needs star_catalogue: the magnitudes go with its stars, one each')
     if not own_set and frames.imported:
         raise ValueError('the frame set has been imported already: its planes no longer hold the frames')
+    if star_catalogue_from not in ('reference', 'coadd'):
+        raise ValueError(f"star_catalogue_from must be 'reference' or 'coadd', not {star_catalogue_from!r}")
+    if coadd_order not in (1, 3):
+        raise ValueError(f'coadd_order must be 1 or 3, not {coadd_order!r}')
+    if coadd_combine not in (None,) + tuple(_lib.COADD_COMBINE):
+        raise ValueError(f'coadd_combine must be None or one of {tuple(_lib.COADD_COMBINE)}, not {coadd_combine!r}')
     margin = n_star / 2.0 if footprint_margin is None else float(footprint_margin)
     exclusion = n_roi / 2.0 if roi_exclusion_radius is None else float(roi_exclusion_radius)
 
@@ -219,7 +234,19 @@ def light_curves_from_frames(frames, exptimes, roi_xy, point_sources_xy, *, refe
         common = common_footprint(footprints[alive])
 
         # ---- 4 stars -------------------------------------------------------------------------------------------------
-        if star_catalogue is None:
+        coadd = None
+        if star_catalogue is None and star_catalogue_from == 'coadd':
+            began = time.perf_counter()
+            coadd = coadd_frames(fs, results, alive, flux_scale=relative_flux_scales(tables, results, int(reference)),
+                                 order=int(coadd_order),
+                                 combine=coadd_combine or ('median' if len(alive) < 11 else 'sigma_clip'))
+            with np.errstate(divide='ignore'):
+                coadd['sources_table'] = extract_stars(coadd['image'], 1.0 / coadd['weight'], ctx=ctx)
+            stars = reference_star_catalogue(coadd['sources_table'], roi, exclusion)
+            mags = None
+            seconds['coadd'] = time.perf_counter() - began
+            clock += seconds['coadd']                                      # not part of the lap that follows
+        elif star_catalogue is None:
             stars = reference_star_catalogue(tables[int(reference)], roi, exclusion)
             mags = None
         else:
@@ -334,4 +361,6 @@ def light_curves_from_frames(frames, exptimes, roi_xy, point_sources_xy, *, refe
                sources_tables=tables, psf_results=psf_results, psf_chi2=psf_chi2, seeing_pixels=seeing,
                ellipticity=ellipticity, background_rms=background_rms, angles=angles, scales=scales, roi_origin=roi_origin,
                point_sources_in_stamps=in_stamps, seconds=seconds)
+    if coadd is not None:
+        out['coadd'] = coadd
     return out

@@ -421,6 +421,42 @@ int lc_frames_coadd(lc_frames *f, int n, const int32_t *frame /*[n]*/, const dou
                     int x0, int y0, const lc_coadd_cfg *cfg, float *image /*[H][W]*/, float *weight_out /*nullable*/,
                     int32_t *count /*nullable*/, int32_t *n_rejected /*nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- cosmic rays of whole frames: astroscrappy.detect_cosmics as upstream applies it, to an image of any size ----------
+ * DESIGN.md section 5 "Cosmic rays of whole frames"; csrc/cosmics_frames.hip.  The SPEC of lc_detect_cosmics with "the
+ * stamp" read as the frame of h x w pixels: the border rule of every median pass, the dilations, the 5 x 5 window of the
+ * cleaning and the outermost ring of the 2x grid are the FRAME's, whatever the tiling.  One call over K frames gives the
+ * bits of the SPEC's float32 restatement on each whole frame; the result depends neither on K nor on scratch_frames.
+ *   lc_detect_cosmics_frames: host pointers, the frame twin of lc_detect_cosmics.  data, invar (nullable), inmask
+ *   (nullable) [K][h][w] as there.  crmask [K][h][w]; clean [K][h][w] = the cleaned counts / gain; iters [K]; n_flagged
+ *   [K] = the pixels of crmask; kernel_ms = device time of all launches (HIP events).
+ *   lc_frames_detect_cosmics: the same on the resident planes of a set, slot k of the n slots being plane frame[k].
+ *   noise_from_rms = 1: invar is formed on the device as the square, in float32, of the noise map lc_frames_cut_stamps
+ *   and lc_frames_aperture_sums form from exptime and rms ([K], by plane; after an import both default to the recorded
+ *   values, LC_ERR_INVALID when neither is there).  noise_from_rms = 0: the SPEC's noise model from the data and
+ *   readnoise.  inmask, crmask, clean [n][h][w], iters, n_flagged [n]: by slot, each nullable.  apply: 0 leaves the
+ *   planes as they are; LC_COSMICS_SET_NAN sets the flagged pixels of the planes to NaN (what lc_frames_coadd and the
+ *   NaN rule of lc_frames_cut_stamps treat as missing); LC_COSMICS_SET_CLEAN replaces them by clean.
+ * Frames are processed in chunks of scratch_frames frames (0: as many as fit a budget of 128 MiB, at least one): 6 bytes
+ * of scratch per pixel, 10 with a variance.  Any h, w >= 8 with h w < 2^31 (lc_cosmics_frames_supported, no device
+ * needed; LC_ERR_UNSUPPORTED otherwise).  Only sepmed = 1 is built for frames: sepmed = 0, and cleantype / fsmode other
+ * than 0, return LC_ERR_UNSUPPORTED.
+ *   Checked on the host before anything is launched, the outputs untouched, LC_ERR_INVALID: K or n < 1, a missing data,
+ *   cfg, crmask (host-pointer form) or frame list; in the frames form no output at all with apply = 0, a frame index
+ *   outside [0, K), a frame listed twice with apply != 0, an unknown apply, an exptime that is not finite or not > 0;
+ *   the settings lc_detect_cosmics refuses; scratch_frames < 0. */
+#define LC_COSMICS_SET_NAN 1
+#define LC_COSMICS_SET_CLEAN 2
+int lc_cosmics_frames_supported(int h, int w);
+int lc_detect_cosmics_frames(lc_ctx *ctx, int K, int h, int w, const float *data, const float *invar /*nullable*/,
+                             const uint8_t *inmask /*nullable*/, const lc_cosmics_cfg *cfg, int scratch_frames,
+                             uint8_t *crmask /*[K][h][w]*/, float *clean /*nullable*/, int32_t *iters /*nullable*/,
+                             int32_t *n_flagged /*nullable, [K]*/, float *kernel_ms /*nullable*/);
+int lc_frames_detect_cosmics(lc_frames *f, int n, const int32_t *frame /*[n]*/, const float *exptime /*[K] nullable*/,
+                             const float *rms /*[K] nullable*/, int noise_from_rms, const uint8_t *inmask /*[n][h][w] nullable*/,
+                             const lc_cosmics_cfg *cfg, int apply, int scratch_frames, uint8_t *crmask /*nullable*/,
+                             float *clean /*nullable*/, int32_t *iters /*nullable*/, int32_t *n_flagged /*nullable*/,
+                             float *kernel_ms /*nullable*/);
+
 /* ---- registration of source lists by star triangles (astroalign.find_transform), batched ----------------------------------
  * The reference gives a frame its WCS from another frame's, or from Gaia positions, with one astroalign.find_transform per
  * frame (lightcurver/processes/alternate_plate_solving_adapt_existing_wcs.py:24, alternate_plate_solving_with_gaia.py:66).

@@ -65,6 +65,7 @@ class CoaddCfg(C.Structure):
 
 
 COADD_COMBINE = {'mean': 0, 'median': 1, 'sigma_clip': 2}   # LC_COADD_* of include/lcmi.h
+COSMICS_APPLY = {None: 0, 'nan': 1, 'clean': 2}             # 0, LC_COSMICS_SET_NAN, LC_COSMICS_SET_CLEAN
 
 
 class BackgroundCfg(C.Structure):
@@ -172,6 +173,11 @@ SIGNATURES = {
     'lc_frames_aperture_sums': (C.c_int, [vp, C.c_int, ip, dp, dp, fp, fp, C.c_int, dp, dp, dp, dp, C.POINTER(C.c_float)]),
     'lc_frames_coadd': (C.c_int, [vp, C.c_int, ip, dp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CoaddCfg), fp, fp,
                                   ip, ip, C.POINTER(C.c_float)]),
+    'lc_cosmics_frames_supported': (C.c_int, [C.c_int, C.c_int]),
+    'lc_detect_cosmics_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_uint8), C.POINTER(CosmicsCfg),
+                                           C.c_int, C.POINTER(C.c_uint8), fp, ip, ip, C.POINTER(C.c_float)]),
+    'lc_frames_detect_cosmics': (C.c_int, [vp, C.c_int, ip, fp, fp, C.c_int, C.POINTER(C.c_uint8), C.POINTER(CosmicsCfg),
+                                           C.c_int, C.c_int, C.POINTER(C.c_uint8), fp, ip, ip, C.POINTER(C.c_float)]),
     'lc_register_supported': (C.c_int, [C.c_int]),
     'lc_register_sources': (C.c_int, [vp, C.c_int, C.c_int, dp, ip, dp, ip, C.POINTER(RegisterCfg), dp, ip, ip, ip, ip,
                                       C.POINTER(C.c_float)]),

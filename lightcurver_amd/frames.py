@@ -215,6 +215,66 @@ class FrameSet:
         out['kernel_ms'] = ms.value
         return out
 
+    def detect_cosmics(self, frame_index=None, exptimes=None, background_rms=None, noise=None, inmask=None, apply=None,
+                       cosmics_masking_params=None, download=('crmask',), scratch_frames=0):
+        """The cosmic rays of whole frames, on the resident planes in one device call (``lc_frames_detect_cosmics``;
+        DESIGN.md section 5 "Cosmic rays of whole frames").  frame_index: the frames to take (default: all).  noise
+        'rms': the variance is the square of the noise map ``cut_stamps`` forms, from exptimes and background_rms (one
+        per frame of the set, or one for all; after ``import_frames`` both default to the recorded values); 'model': the
+        SPEC's noise model from the data and ``readnoise``.  The default is 'rms' on an imported set and 'model'
+        otherwise.  inmask: (n, h, w) bool, one per listed frame.  apply: None leaves the planes as they are; 'nan' sets
+        the flagged pixels of the planes to NaN, which ``coadd`` and ``cut_stamps`` treat as missing; 'clean' replaces
+        them by the cleaned values (a frame may then be listed once only).  cosmics_masking_params: the reference's
+        dict, as ``cut_stamps`` takes it; only ``sepmed=True`` is built for frames.  download: which of 'crmask' and
+        'clean' come back to the host: with ``download=()`` no frame-sized array moves.  ``scratch_frames``: frames per
+        chunk (0: from a budget); the result does not depend on it.  Returns dict(crmask (n, h, w) bool or None, clean
+        (n, h, w) float32 or None, iters, n_flagged int32 (n,), kernel_ms)."""
+        from .processes.cutout_making import _mask_settings
+        handle = self._handle()
+        K, h, w = self.shape
+        frame = np.arange(K, dtype=np.int32) if frame_index is None else \
+            np.ascontiguousarray(np.asarray(frame_index, np.int32).reshape(-1))
+        n = len(frame)
+        if n < 1:
+            raise ValueError('detect_cosmics: no frame')
+        if ((frame < 0) | (frame >= K)).any():
+            raise ValueError(f'detect_cosmics: a frame index outside 0 .. {K - 1}')
+        if apply not in _lib.COSMICS_APPLY:
+            raise ValueError(f'detect_cosmics: apply must be one of {tuple(_lib.COSMICS_APPLY)}, not {apply!r}')
+        if apply is not None and len(np.unique(frame)) != n:
+            raise ValueError('detect_cosmics: a frame listed twice with apply')
+        noise = ('rms' if self.imported else 'model') if noise is None else noise
+        if noise not in ('rms', 'model'):
+            raise ValueError(f"detect_cosmics: noise must be 'rms' or 'model', not {noise!r}")
+        unknown = set(download) - {'crmask', 'clean'}
+        if unknown:
+            raise ValueError(f'detect_cosmics: download takes crmask and clean, not {sorted(unknown)}')
+        ccfg, _ = _mask_settings(dict(cosmics_masking_params or {}))
+        if not ccfg.sepmed:
+            raise NotImplementedError('detect_cosmics: only the separable medians (sepmed=True) are built for frames')
+        if not self._l.lc_cosmics_frames_supported(h, w):
+            raise _lib.LcError(f'lc_frames_detect_cosmics takes frames of h, w >= 8 with h w < 2^31, not {h} x {w}')
+        t, rms = (_per_frame(exptimes, K), _per_frame(background_rms, K)) if noise == 'rms' else (None, None)
+        if t is not None and not (np.isfinite(t) & (t > 0)).all():
+            raise ValueError('exposure times must be finite and > 0')
+        m = None
+        if inmask is not None:
+            m = np.ascontiguousarray(np.asarray(inmask).astype(np.uint8))
+            if m.shape != (n, h, w):
+                raise ValueError(f'detect_cosmics: inmask must have the shape {(n, h, w)}')
+        cr = np.empty((n, h, w), np.uint8) if 'crmask' in download else None
+        clean = np.empty((n, h, w), np.float32) if 'clean' in download else None
+        iters = np.empty(n, np.int32)
+        flagged = np.empty(n, np.int32)
+        u8 = lambda a: None if a is None else a.ctypes.data_as(_u8p)
+        ms = C.c_float()
+        self.ctx.check(self._l.lc_frames_detect_cosmics(
+            handle, n, frame.ctypes.data_as(_i32p), ptr(t), ptr(rms), int(noise == 'rms'), u8(m), C.byref(ccfg),
+            _lib.COSMICS_APPLY[apply], int(scratch_frames), u8(cr), ptr(clean), iters.ctypes.data_as(_i32p),
+            flagged.ctypes.data_as(_i32p), C.byref(ms)), 'lc_frames_detect_cosmics')
+        return dict(crmask=None if cr is None else cr.astype(bool), clean=clean, iters=iters, n_flagged=flagged,
+                    kernel_ms=ms.value)
+
     def close(self):
         if getattr(self, 'h', None):
             self._l.lc_frames_destroy(self.h)

@@ -30,12 +30,16 @@ def relative_flux_scales(source_tables, results, reference=0):
     return out
 
 
-def coadd_frames(fs, results, frames=None, flux_scale=None, weights=None, **kw):
+def coadd_frames(fs, results, frames=None, flux_scale=None, weights=None, reject_cosmics=None, **kw):
     """``FrameSet.coadd`` of the frames that ``register_frames`` solved: ``results`` is its list, one entry per frame of
     ``fs``; ``frames`` (default: all) the frames to take, of which those that failed are skipped.  flux_scale, weights:
     None, or one value per frame of the SET (as ``relative_flux_scales`` returns them), indexed like ``results``; a frame
     whose flux scale is not finite is skipped too.  The grid defaults to the reference frame's (``shape``, ``origin`` and
-    everything else go to ``FrameSet.coadd``).  Returns its dict plus ``frames``: the frames that went in."""
+    everything else go to ``FrameSet.coadd``).  reject_cosmics: None, or a dict of ``cosmics_masking_params`` (``{}``: the
+    defaults): ``fs.detect_cosmics(apply='nan', download=())`` then runs on the frames about to be stacked, so that a
+    cosmic is missing from its frame's samples whatever ``combine`` is, with 'mean' too and with a handful of frames.  The
+    planes KEEP those NaNs afterwards: a later ``cut_stamps`` sees them as the NaN rule prescribes.  Returns the dict of
+    ``FrameSet.coadd`` plus ``frames``: the frames that went in."""
     K = len(results)
     take = np.arange(K) if frames is None else np.asarray(frames, np.int64).reshape(-1)
     per_set = lambda a: None if a is None else np.broadcast_to(np.asarray(a, np.float64).reshape(-1), (K,))
@@ -43,6 +47,8 @@ def coadd_frames(fs, results, frames=None, flux_scale=None, weights=None, **kw):
     used = np.array([k for k in take if results[k]['success'] and (g is None or np.isfinite(g[k]))], dtype=np.int64)
     if not len(used):
         raise ValueError('coadd_frames: no registered frame to co-add')
+    if reject_cosmics is not None:
+        fs.detect_cosmics(np.unique(used), apply='nan', cosmics_masking_params=dict(reject_cosmics), download=())
     out = fs.coadd(used, [results[k]['transform'] for k in used], flux_scale=None if g is None else g[used],
                    weights=None if w is None else w[used], **kw)
     out['frames'] = used

@@ -421,6 +421,60 @@ int lc_frames_coadd(lc_frames *f, int n, const int32_t *frame /*[n]*/, const dou
                     int x0, int y0, const lc_coadd_cfg *cfg, float *image /*[H][W]*/, float *weight_out /*nullable*/,
                     int32_t *count /*nullable*/, int32_t *n_rejected /*nullable*/, float *kernel_ms /*nullable*/);
 
+/* ---- difference imaging: a reference image PSF-matched to each frame and subtracted ---------------------------------
+ * DESIGN.md section 5 "Difference imaging" is the SPEC; csrc/diffim.hip.  Per frame k and region g of a gy x gx grid
+ * (rows [i H / gy, (i + 1) H / gy), columns likewise) the (2r + 1)^2 free pixel values of a convolution kernel and a
+ * polynomial background of degree bg_degree (terms 1, X, Y, X^2, XY, Y^2 of the region's coordinates in [-1, 1]) are
+ * fitted by least squares so that M = reference (*) kernel + background matches the frame (a true convolution, indexed
+ * as scipy.signal.convolve2d(reference, kernel, mode='same')), with clip_iters further rounds that leave out the pixels
+ * with |D| > n_sigma sigma.  sigma: sqrt(var) where variances are given, else sigma[k], else the previous round's
+ * residual rms.  The normal equations are summed in float64 on the device in a fixed order, solved by Cholesky in
+ * float64 on the host, and D = frame - M is evaluated in float32.  Nothing depends on K, on what else shares the call,
+ * on scratch_frames or on the run, bit for bit.
+ *   lc_diffim_frames: host pointers.  target [K][h][w]; reference [h][w]; var [K][h][w], mask [K][h][w] (nonzero: out
+ *   of the fit, D still computed) and sigma [K] nullable.
+ *   lc_frames_subtract_reference: the same on the resident planes of a set.  Slot k is plane frame[k] resampled onto the
+ *   grid of H x W reference pixels at (x0, y0) exactly as lc_frames_coadd resamples it with flux scale 1 (affine, order:
+ *   as there; a missing sample is NaN and falls out of the fit).  mask [n][H][W], sigma [n]: by slot, nullable.  Frames
+ *   are processed in chunks of scratch_frames (0: as many as fit a budget of 128 MiB, at least one).  The planes stay
+ *   as they are.
+ * Outputs (lc_diffim_out, each nullable, G = gy gx, P = (2r + 1)^2 + 1, 3 or 6): diff [K][h][w] (NaN within r pixels
+ * of the border and wherever the frame or a reference pixel of the footprint is not finite); kernel [K][G][(2r + 1)^2];
+ * bg [K][G][6] (unused entries 0); scale [K][G] = the sum of the kernel; n_used [K][G] = the pixels of the last round's
+ * fit set; chi2 [K][G] = sum over them of D^2 / sigma^2, over n_used - P (with neither var nor sigma, sigma is the last
+ * round's own rms); status [K][G]: 0 ok, 1 n_used < 2 P, 2 a pivot that is not positive (then kernel, bg, scale, chi2
+ * and the region's diff are NaN; the call still returns LC_OK); gram [K][G][P][P] and rhs [K][G][P]: the normal
+ * equations of the last round the region went through.  Beside them split_ms [3], a diagnostic that does not count
+ * as an output: device time of the Gram sums, host time of the solves, device time of the subtraction.  kernel_ms: device time of all kernels.
+ *   Checked on the host before anything is launched, the outputs untouched, LC_ERR_INVALID: K or n < 1; a missing
+ *   target, reference, cfg, out or frame list; no output at all; a frame index outside [0, K); an affine entry that is
+ *   not finite or det = 0; r outside [1, 7], bg_degree outside [0, 2], gy or gx < 1 or gy gx > 64, clip_iters < 0,
+ *   n_sigma not finite or <= 0, an order other than 1 or 3; a sigma that is not finite or not > 0; scratch_frames < 0.
+ *   LC_ERR_UNSUPPORTED: what lc_diffim_supported (no device needed) refuses: h or w < 2 r + 1, h w >= 2^31, a region
+ *   without a pixel, and the ranges above. */
+typedef struct {
+  int32_t r, bg_degree, gy, gx, clip_iters;
+  float n_sigma;
+} lc_diffim_cfg;
+typedef struct {
+  float *diff;
+  double *kernel, *bg, *scale;
+  int32_t *n_used;
+  double *chi2;
+  int32_t *status;
+  double *gram, *rhs;
+  float *split_ms;
+} lc_diffim_out;
+int lc_diffim_supported(int h, int w, int r, int bg_degree, int gy, int gx);
+int lc_diffim_frames(lc_ctx *ctx, int K, int h, int w, const float *target, const float *reference,
+                     const float *var /*nullable*/, const uint8_t *mask /*nullable*/, const float *sigma /*nullable*/,
+                     const lc_diffim_cfg *cfg, const lc_diffim_out *out, float *kernel_ms /*nullable*/);
+int lc_frames_subtract_reference(lc_frames *f, int n, const int32_t *frame /*[n]*/, const double *affine /*[n][6]*/, int H,
+                                 int W, int x0, int y0, int order, const float *reference /*[H][W]*/,
+                                 const float *sigma /*[n] nullable*/, const uint8_t *mask /*[n][H][W] nullable*/,
+                                 const lc_diffim_cfg *cfg, int scratch_frames, const lc_diffim_out *out,
+                                 float *kernel_ms /*nullable*/);
+
 /* ---- cosmic rays of whole frames: astroscrappy.detect_cosmics as upstream applies it, to an image of any size ----------
  * DESIGN.md section 5 "Cosmic rays of whole frames"; csrc/cosmics_frames.hip.  The SPEC of lc_detect_cosmics with "the
  * stamp" read as the frame of h x w pixels: the border rule of every median pass, the dilations, the 5 x 5 window of the

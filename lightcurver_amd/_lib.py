@@ -68,6 +68,21 @@ COADD_COMBINE = {'mean': 0, 'median': 1, 'sigma_clip': 2}   # LC_COADD_* of incl
 COSMICS_APPLY = {None: 0, 'nan': 1, 'clean': 2}             # 0, LC_COSMICS_SET_NAN, LC_COSMICS_SET_CLEAN
 
 
+class DiffimCfg(C.Structure):
+    _fields_ = [('r', C.c_int32), ('bg_degree', C.c_int32), ('gy', C.c_int32), ('gx', C.c_int32),
+                ('clip_iters', C.c_int32), ('n_sigma', C.c_float)]
+
+
+# lc_diffim_out of include/lcmi.h: name -> element type, in the order of the struct
+DIFFIM_OUT_FIELDS = (('diff', C.c_float), ('kernel', C.c_double), ('bg', C.c_double), ('scale', C.c_double),
+                     ('n_used', C.c_int32), ('chi2', C.c_double), ('status', C.c_int32), ('gram', C.c_double),
+                     ('rhs', C.c_double), ('split_ms', C.c_float))
+
+
+class DiffimOut(C.Structure):
+    _fields_ = [(name, C.POINTER(t)) for name, t in DIFFIM_OUT_FIELDS]
+
+
 class BackgroundCfg(C.Structure):
     _fields_ = [('bw', C.c_int32), ('bh', C.c_int32), ('fw', C.c_int32), ('fh', C.c_int32), ('fthresh', C.c_float)]
 
@@ -173,6 +188,12 @@ SIGNATURES = {
     'lc_frames_aperture_sums': (C.c_int, [vp, C.c_int, ip, dp, dp, fp, fp, C.c_int, dp, dp, dp, dp, C.POINTER(C.c_float)]),
     'lc_frames_coadd': (C.c_int, [vp, C.c_int, ip, dp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CoaddCfg), fp, fp,
                                   ip, ip, C.POINTER(C.c_float)]),
+    'lc_diffim_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'lc_diffim_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(C.c_uint8), fp, C.POINTER(DiffimCfg),
+                                   C.POINTER(DiffimOut), C.POINTER(C.c_float)]),
+    'lc_frames_subtract_reference': (C.c_int, [vp, C.c_int, ip, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp,
+                                               C.POINTER(C.c_uint8), C.POINTER(DiffimCfg), C.c_int, C.POINTER(DiffimOut),
+                                               C.POINTER(C.c_float)]),
     'lc_cosmics_frames_supported': (C.c_int, [C.c_int, C.c_int]),
     'lc_detect_cosmics_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_uint8), C.POINTER(CosmicsCfg),
                                            C.c_int, C.POINTER(C.c_uint8), fp, ip, ip, C.POINTER(C.c_float)]),

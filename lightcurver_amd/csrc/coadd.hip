@@ -22,6 +22,7 @@
 #include "device_call.h"
 #include "frames_state.h"
 #include "lc_common.h"
+#include "resample_device.h"
 #include "../../include/lcmi.h"
 
 namespace lc {
@@ -41,31 +42,6 @@ struct CoaddWarpArgs {
   float *samples;         // [n][rows][W]
 };
 
-// Keys' cubic convolution with a = -1/2 at offset t in [0, 1): the weights of the taps f - 1 .. f + 2
-__device__ __forceinline__ void co_cubic(float t, float w[4]) {
-  w[0] = ((2.0f - t) * t - 1.0f) * t / 2.0f;
-  w[1] = ((3.0f * t - 5.0f) * t * t + 2.0f) / 2.0f;
-  w[2] = ((4.0f - 3.0f * t) * t + 1.0f) * t / 2.0f;
-  w[3] = (t - 1.0f) * t * t / 2.0f;
-}
-
-template <int TAPS>
-__device__ __forceinline__ float co_sample(const float *img, int w, int ty, int tx, const float *wy, const float *wx) {
-  float v = 0.0f;
-#pragma unroll
-  for (int a = 0; a < TAPS; ++a) {
-    const float *row = img + (size_t)(ty + a) * w + tx;
-#pragma unroll
-    for (int b = 0; b < TAPS; ++b) {
-      float t = row[b];
-      t = t * wy[a];
-      t = t * wx[b];
-      v = v + t;
-    }
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(kCoThreads) void coadd_warp_kernel(CoaddWarpArgs A) {
   const int tiles = (A.W + kCoThreads - 1) / kCoThreads;
   const size_t b = blockIdx.x;
@@ -75,27 +51,8 @@ __global__ __launch_bounds__(kCoThreads) void coadd_warp_kernel(CoaddWarpArgs A)
   const int j = tile * kCoThreads + threadIdx.x;
   if (j >= A.W || k >= A.n) return;
   const double *M = A.affine + (size_t)k * 6;
-  const double x = (double)(A.x0 + j), y = (double)(A.row0 + r);
-  const double xs = (M[0] * x + M[1] * y) + M[2], ys = (M[3] * x + M[4] * y) + M[5];
-  const double fx = floor(xs), fy = floor(ys);
-  const float tx = (float)(xs - fx), ty = (float)(ys - fy);
-  const int before = A.order == 3 ? 1 : 0, after = A.order == 3 ? 2 : 1;
-  float v = __builtin_nanf("");
-  // (a coordinate that is not finite fails every comparison)
-  if (fx >= (double)before && fx <= (double)(A.w - 1 - after) && fy >= (double)before && fy <= (double)(A.h - 1 - after)) {
-    const float *img = A.planes + (size_t)A.frame[k] * A.h * A.w;
-    const int ix = (int)fx - before, iy = (int)fy - before;
-    if (A.order == 3) {
-      float wy[4], wx[4];
-      co_cubic(ty, wy);
-      co_cubic(tx, wx);
-      v = co_sample<4>(img, A.w, iy, ix, wy, wx);
-    } else {
-      const float wy[2] = {1.0f - ty, ty}, wx[2] = {1.0f - tx, tx};
-      v = co_sample<2>(img, A.w, iy, ix, wy, wx);
-    }
-    v = v * A.scale[k];
-  }
+  const float v = co_resample(A.planes + (size_t)A.frame[k] * A.h * A.w, A.h, A.w, M, (double)(A.x0 + j),
+                              (double)(A.row0 + r), A.order, A.scale[k]);
   A.samples[((size_t)k * A.rows + r) * A.W + j] = v;
 }
 

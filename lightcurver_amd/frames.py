@@ -215,6 +215,62 @@ class FrameSet:
         out['kernel_ms'] = ms.value
         return out
 
+    def subtract_reference(self, frame_index, transforms, reference, origin=(0, 0), order=3, r=3, bg_degree=1,
+                           regions=(1, 1), clip_iters=2, n_sigma=4.0, sigma=None, mask=None,
+                           download=('diff', 'kernel', 'bg', 'scale', 'n_used', 'chi2', 'status'), scratch_frames=0):
+        """Difference imaging on the resident planes in one device call (``lc_frames_subtract_reference``; DESIGN.md
+        section 5 "Difference imaging").  The frames ``frame_index`` are resampled onto the grid of ``reference`` (H, W)
+        at ``origin`` (x0, y0) exactly as ``coadd`` resamples them (transforms, order: as there), and per frame and region
+        the reference is matched to the frame and subtracted (r, bg_degree, regions, clip_iters, n_sigma, mask, download
+        and the returned dict: as ``processes.difference_imaging.match_and_subtract``; mask (n, H, W), by listed frame).
+        sigma: the pixel noise per listed frame, for the clipping and chi2; by default, after ``import_frames``, the
+        recorded ``globalrms`` times |det| of the transform; an error when neither is there.  ``scratch_frames``: frames
+        per chunk (0: from a budget); the result does not depend on it.  The planes stay as they are."""
+        from .processes import difference_imaging as di
+        what = 'subtract_reference'
+        handle = self._handle()
+        K = self.shape[0]
+        frame = np.ascontiguousarray(np.asarray(frame_index, np.int32).reshape(-1))
+        n = len(frame)
+        if n < 1:
+            raise ValueError(f'{what}: no frame')
+        if ((frame < 0) | (frame >= K)).any():
+            raise ValueError(f'{what}: a frame index outside 0 .. {K - 1}')
+        if hasattr(transforms, 'params') or (isinstance(transforms, np.ndarray) and transforms.ndim == 2):
+            transforms = [transforms]
+        if len(transforms) != n:
+            raise ValueError(f'{what}: {n} frames but {len(transforms)} transforms')
+        affine = np.empty((n, 6), np.float64)
+        for k, t in enumerate(transforms):
+            m = np.asarray(t.params if hasattr(t, 'params') else t, np.float64)
+            if m.shape not in ((2, 3), (3, 3)):
+                raise ValueError(f'{what}: a transform of shape {m.shape}, not (2, 3) or (3, 3)')
+            affine[k] = m[:2].reshape(6)
+        ref = f32(reference)
+        if ref.ndim != 2 or 0 in ref.shape:
+            raise ValueError(f'{what}: the reference must be a 2-D image, got {ref.shape}')
+        H, W = ref.shape
+        if order not in (1, 3):
+            raise ValueError(f'{what}: order must be 1 or 3, not {order!r}')
+        if int(scratch_frames) < 0:
+            raise ValueError(f'{what}: scratch_frames must be >= 0')
+        cfg, gy, gx = di._settings((H, W), r, bg_degree, regions, clip_iters, n_sigma, download, what)
+        if sigma is None:
+            if not self.imported:
+                raise ValueError(f'{what}: sigma is needed on a set that has not been imported')
+            det = np.abs(affine[:, 0] * affine[:, 4] - affine[:, 1] * affine[:, 3])
+            sigma = self._globalrms[frame].astype(np.float64) * det
+        s = di._per_slot(sigma, n, what)
+        m = di._mask(mask, (n, H, W), what)
+        arrays, struct = di._outputs(n, (H, W), cfg, download)
+        ms = C.c_float()
+        self.ctx.check(self._l.lc_frames_subtract_reference(
+            handle, n, frame.ctypes.data_as(_i32p), affine.ctypes.data_as(_lib.dp), H, W, int(origin[0]), int(origin[1]),
+            int(order), ptr(ref), ptr(s), None if m is None else m.ctypes.data_as(_u8p), C.byref(cfg), int(scratch_frames),
+            C.byref(struct), C.byref(ms)), 'lc_frames_subtract_reference')
+        arrays['kernel_ms'] = ms.value
+        return arrays
+
     def detect_cosmics(self, frame_index=None, exptimes=None, background_rms=None, noise=None, inmask=None, apply=None,
                        cosmics_masking_params=None, download=('crmask',), scratch_frames=0):
         """The cosmic rays of whole frames, on the resident planes in one device call (``lc_frames_detect_cosmics``;

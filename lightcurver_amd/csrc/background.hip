@@ -14,6 +14,7 @@
 #include <cstring>
 #include <vector>
 
+#include "block_reduce.h"
 #include "device_call.h"
 #include "frame_steps.h"
 #include "lc_common.h"
@@ -35,26 +36,6 @@ struct BgGrid {
 };
 
 typedef unsigned long long u64;
-
-template <class T>
-__device__ __forceinline__ T bg_wave_sum(T v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  return v;
-}
-
-// the sum over the workgroup's Waves waves in a fixed order, returned to every lane; part is LDS of Waves values
-template <int Waves, class T>
-__device__ __forceinline__ T bg_block_sum(T v, T *part) {
-  v = bg_wave_sum(v);
-  if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = v;
-  __syncthreads();
-  T r = part[0];
-#pragma unroll
-  for (int wv = 1; wv < Waves; ++wv) r += part[wv];
-  __syncthreads();
-  return r;
-}
 
 struct BgStatArgs {
   BgGrid g;
@@ -110,9 +91,9 @@ __global__ __launch_bounds__(kBgStatThreads) void bg_stats_kernel(BgStatArgs A) 
       ++n;
     }
   });
-  sum = bg_block_sum<kBgStatWaves>(sum, s_pd);
-  sq = bg_block_sum<kBgStatWaves>(sq, s_pd);
-  n = bg_block_sum<kBgStatWaves>(n, s_pu);
+  sum = block_sum<kBgStatWaves>(sum, s_pd);
+  sq = block_sum<kBgStatWaves>(sq, s_pd);
+  n = block_sum<kBgStatWaves>(n, s_pu);
   if (2 * n < (u64)count) {  // fewer good pixels than half of the mesh: bad
     if (tid == 0) A.raw_back[out] = A.raw_rms[out] = nanf_;
     return;
@@ -131,9 +112,9 @@ __global__ __launch_bounds__(kBgStatThreads) void bg_stats_kernel(BgStatArgs A) 
       ++n;
     }
   });
-  sum = bg_block_sum<kBgStatWaves>(sum, s_pd);
-  sq = bg_block_sum<kBgStatWaves>(sq, s_pd);
-  n = bg_block_sum<kBgStatWaves>(n, s_pu);
+  sum = block_sum<kBgStatWaves>(sum, s_pd);
+  sq = block_sum<kBgStatWaves>(sq, s_pd);
+  n = block_sum<kBgStatWaves>(n, s_pu);
   if (n == 0) {  // nothing inside the cuts (this project's rule): bad
     if (tid == 0) A.raw_back[out] = A.raw_rms[out] = nanf_;
     return;
@@ -219,8 +200,8 @@ __global__ __launch_bounds__(kBgStatThreads) void bg_stats_kernel(BgStatArgs A) 
       s1 += ci;
       s2 += ci * (u64)i;
     }
-    s1 = bg_block_sum<kBgStatWaves>(s1, s_pu);
-    s2 = bg_block_sum<kBgStatWaves>(s2, s_pu);
+    s1 = block_sum<kBgStatWaves>(s1, s_pu);
+    s2 = block_sum<kBgStatWaves>(s2, s_pu);
     if (total) {
       mea = (double)s1 / (double)total;
       sig = (double)s2 / (double)total - mea * mea;

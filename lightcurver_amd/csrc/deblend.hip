@@ -18,8 +18,10 @@
 //                         the pixels take the union's label, count[label] its pixels; then (extract.hip) a third time;
 //   db_finish_kernel      the first max_objects rows into the caller's table with the NODEBLEND bit, nobj and status 1.
 // As in extract.hip no workgroup waits for another within a launch; every loop over labels or targets is bounded and
-// the bound sets status 2.  The tree walk is a copy of segment.hip's device functions for a rectangular box, kept apart
-// so that segment_kernel's code object does not change (DESIGN.md says so).  Offsets into the planes are 64-bit.
+// the bound sets status 2.  The tree walk is still a copy, of deblend_tree.h's device functions (segment_kernel's) without
+// the groups of a stamp: instantiated from that header this kernel measured 4 to 6 % slower for a reason that was not
+// found (DESIGN.md gives the figures), so the copy stays until it is.  The shape and the wing of clean are clean_shape.h,
+// shared with segment_kernel.  Offsets into the planes are 64-bit.
 #pragma clang fp contract(off)  // the SPEC fixes every rounding: no fused multiply-adds, on the device or the host
 
 #include <climits>
@@ -28,6 +30,8 @@
 #include <cstring>
 #include <vector>
 
+#include "block_reduce.h"
+#include "clean_shape.h"
 #include "device_call.h"
 #include "frame_steps.h"
 #include "lc_common.h"
@@ -433,25 +437,6 @@ __global__ __launch_bounds__(kDbThreads) void db_deblend_kernel(DbDeblendArgs A)
 
 // ---- clean ----------------------------------------------------------------------------------------------------------------
 
-struct DbShape {
-  double x, y, a, cxx, cyy, cxy, unit, amp, mth;
-  long long s0;
-  int npix, valid;
-};
-
-template <class T>
-__device__ __forceinline__ T db_block_sum(T v, T *part) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T r = part[0];
-#pragma unroll
-  for (int wv = 1; wv < kDbWaves; ++wv) r += part[wv];
-  __syncthreads();
-  return r;
-}
-
 struct DbCleanArgs {
   int K, h, w, cap;  // cap: rows of the objects' tables per frame
   int minarea, max_objects;
@@ -461,7 +446,7 @@ struct DbCleanArgs {
   const lc_extract_object *fobj;
   int32_t *label, *count, *status;
   uint8_t *nodeblend;
-  DbShape *shape;
+  CleanShape *shape;  // valid = 0: no part in clean
   int32_t *target, *root, *minlab, *unpix;
   lc_extract_object *objects;
   int32_t *nobj;
@@ -482,7 +467,7 @@ __global__ __launch_bounds__(kDbThreads) void db_shape_kernel(DbCleanArgs A) {
     const bool boxed = !(xmin < 0 || ymin < 0 || xmax >= A.w || ymax >= A.h || xmin > xmax || ymin > ymax);
     if (!boxed || (A.fobj[s].flag & 3)) {  // LARGE or RANGE: no part in clean
       if (tid == 0) {
-        DbShape z;
+        CleanShape z;
         memset(&z, 0, sizeof(z));
         A.shape[s] = z;
       }
@@ -505,12 +490,12 @@ __global__ __launch_bounds__(kDbThreads) void db_shape_kernel(DbCleanArgs A) {
       syy += q * dy * dy;
       sxy += q * dx * dy;
     }
-    s0 = db_block_sum(s0, s_u);
-    sx = db_block_sum(sx, s_u);
-    sy = db_block_sum(sy, s_u);
-    sxx = db_block_sum(sxx, s_u);
-    syy = db_block_sum(syy, s_u);
-    sxy = db_block_sum(sxy, s_u);
+    s0 = block_sum<kDbWaves>(s0, s_u);
+    sx = block_sum<kDbWaves>(sx, s_u);
+    sy = block_sum<kDbWaves>(sy, s_u);
+    sxx = block_sum<kDbWaves>(sxx, s_u);
+    syy = block_sum<kDbWaves>(syy, s_u);
+    sxy = block_sum<kDbWaves>(sxy, s_u);
     // the minarea-th largest snr: its bits, built from the top bit down (a detected snr is positive)
     unsigned kth = 0;
     if (npix >= A.minarea) {
@@ -522,38 +507,15 @@ __global__ __launch_bounds__(kDbThreads) void db_shape_kernel(DbCleanArgs A) {
           const size_t g = base + (size_t)(ymin + (int)r) * A.w + (xmin + (int)c);
           if (A.label[g] == first && __float_as_uint(A.snr[g]) >= cand) ++cnt;
         }
-        if (db_block_sum(cnt, s_i) >= A.minarea) kth = cand;
+        if (block_sum<kDbWaves>(cnt, s_i) >= A.minarea) kth = cand;
       }
     }
     if (tid == 0) {
-      DbShape z;
+      CleanShape z;
       memset(&z, 0, sizeof(z));
-      if (s0 > 0) {
-        const double t = (double)s0, twelfth = 1.0 / 12.0;
-        const double mx = (double)sx / t, my = (double)sy / t;
-        const double x2 = fmax((double)sxx / t - mx * mx, twelfth), y2 = fmax((double)syy / t - my * my, twelfth);
-        double xy = (double)sxy / t - mx * my;
-        double det = x2 * y2 - xy * xy;
-        if (det < 1.0 / 144.0) {
-          xy = 0.0;
-          det = x2 * y2;
-        }
-        const double half = 0.5 * (x2 + y2), dif = x2 - y2;
-        const double root = sqrt(fmax(0.25 * (dif * dif) + xy * xy, 0.0));
-        const double aa = sqrt(half + root), bb = sqrt(fmax(half - root, twelfth));
-        z.x = (double)xmin + mx;
-        z.y = (double)ymin + my;
-        z.a = aa;
-        z.cxx = y2 / det;
-        z.cyy = x2 / det;
-        z.cxy = -2.0 * xy / det;
-        z.unit = M_PI * aa * bb;
-        z.amp = (t * (1.0 / kDbMomentFix)) / (2.0 * z.unit);
-        z.mth = npix >= A.minarea ? fmax((double)__uint_as_float(kth) - (double)A.thresh, 0.0) : 0.0;
-        z.s0 = (long long)s0;
-        z.npix = npix;
-        z.valid = 1;
-      }
+      if (s0 > 0)
+        z = clean_shape((double)s0, (double)sx, (double)sy, (double)sxx, (double)syy, (double)sxy, kDbMomentFix, npix,
+                        A.minarea, kth, A.thresh, (double)xmin, (double)ymin);
       A.shape[s] = z;
     }
   }
@@ -570,22 +532,15 @@ __global__ __launch_bounds__(kDbThreads) void db_target_kernel(DbCleanArgs A) {
   A.unpix[s] = 0;
   int into = -1;
   if (n >= 2) {
-    const DbShape *sh = A.shape + (size_t)frame * A.cap;
-    const DbShape me = sh[i];
+    const CleanShape *sh = A.shape + (size_t)frame * A.cap;
+    const CleanShape me = sh[i];
     if (me.valid) {
       const double thd = (double)A.thresh;
       double best = 0.0;
       for (int j = 0; j < n; ++j) {
-        const DbShape o = sh[j];
+        const CleanShape o = sh[j];
         if (j == i || !o.valid || o.s0 <= me.s0) continue;
-        const double dx = me.x - o.x, dy = me.y - o.y;
-        const double zone = 10.0 * (me.a + o.a);
-        if (dx * dx + dy * dy >= zone * zone) continue;
-        const double ratio = o.amp / thd;
-        if (ratio <= 1.0) continue;
-        const double alpha = (ratio - 1.0) * o.unit / (double)o.npix;
-        const double val = 1.0 + alpha * (o.cxx * dx * dx + o.cyy * dy * dy + o.cxy * dx * dy);
-        const double wing = (1.0 < val && val < 1e10) ? o.amp / val : 0.0;
+        const double wing = clean_wing(me, o, thd);
         if (wing > me.mth && wing > best) {
           best = wing;
           into = j;

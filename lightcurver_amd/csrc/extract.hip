@@ -22,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "block_reduce.h"
 #include "device_call.h"
 #include "frame_steps.h"
 #include "lc_common.h"
@@ -453,20 +454,6 @@ __global__ __launch_bounds__(kExThreads) void ex_box_kernel(ExBoxArgs A) {
 
 // ---- measurement ---------------------------------------------------------------------------------------------------------
 
-// sums over the workgroup in a fixed order (lanes by shuffles, then the waves in turn), returned to every lane
-template <class T>
-__device__ __forceinline__ T ex_block_sum(T v, T *part) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = v;
-  __syncthreads();
-  T r = part[0];
-#pragma unroll
-  for (int wv = 1; wv < kExWaves; ++wv) r += part[wv];
-  __syncthreads();
-  return r;
-}
-
 struct ExMeasureArgs {
   ExGeom g;
   int K, max_objects;
@@ -532,13 +519,13 @@ __global__ __launch_bounds__(kExThreads) void ex_measure_kernel(ExMeasureArgs A)
         ++r;
       }
     }
-    s0 = ex_block_sum(s0, s_u);
-    sx = ex_block_sum(sx, s_u);
-    sy = ex_block_sum(sy, s_u);
-    sxx = ex_block_sum(sxx, s_u);
-    syy = ex_block_sum(syy, s_u);
-    sxy = ex_block_sum(sxy, s_u);
-    flux = ex_block_sum(flux, s_d);
+    s0 = block_sum<kExWaves>(s0, s_u);
+    sx = block_sum<kExWaves>(sx, s_u);
+    sy = block_sum<kExWaves>(sy, s_u);
+    sxx = block_sum<kExWaves>(sxx, s_u);
+    syy = block_sum<kExWaves>(syy, s_u);
+    sxy = block_sum<kExWaves>(sxy, s_u);
+    flux = block_sum<kExWaves>(flux, s_d);
     // the maxima: the larger snr, of equals the earlier pixel
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) {

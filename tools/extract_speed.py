@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 from lightcurver_amd import _lib  # noqa: E402
+if os.environ.get('LCMI_DBG_LIB'): _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), os.environ['LCMI_DBG_LIB'])
 from lightcurver_amd.processes.frame_importation import characterize_frames, import_frames  # noqa: E402
 from tests import _background as B  # noqa: E402
 from tests import _extract as E  # noqa: E402

@@ -10,6 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 from lightcurver_amd import _lib
+if os.environ.get('LCMI_DBG_LIB'): _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), os.environ['LCMI_DBG_LIB'])
 from lightcurver_amd.processes.psf_modelling import mask_surrounding_stars, mask_surrounding_stars_batch
 from lightcurver_amd.processes.source_masking import segment_batch
 from lightcurver_amd.starred.procedures.psf_routines import build_psf_batch

@@ -7,9 +7,8 @@
 //          resample at the shift's coordinates into the second plane, prefilter again, resample at the rotation's
 //          coordinates back into the first, coalesced write.  Coordinates and the in-range test in double.
 //   stack  one lane per (cube, pixel), adjacent lanes adjacent pixels, so every read of an epoch is coalesced.  The
-//          median is the exact order statistic: bitwise bisection on the order-preserving integer key of the float, 32
-//          counting passes over the epochs, both middle elements at once.  Mean, deviation, rejection and the weighted
-//          mean are sequential sums in epoch order: the result does not depend on the launch.
+//          combine is robust_combine of order_stats.h: the median is the exact order statistic, and mean, deviation,
+//          rejection and the weighted mean are sequential sums in epoch order: the result does not depend on the launch.
 #pragma clang fp contract(off)  // the SPEC fixes every rounding, and the coordinates are scipy's own expressions
 
 #include <cmath>
@@ -18,6 +17,7 @@
 
 #include "device_call.h"
 #include "lc_common.h"
+#include "order_stats.h"
 #include "../../include/lcmi.h"
 
 namespace lc {
@@ -161,80 +161,18 @@ struct StackArgs {
   int32_t *nrej;
 };
 
-__device__ __forceinline__ unsigned st_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float st_unkey(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 __global__ __launch_bounds__(kStThreads) void stack_kernel(StackArgs A) {
   const int p = blockIdx.x * kStThreads + threadIdx.x, c = blockIdx.y;
   if (p >= A.np) return;
   const size_t np = (size_t)A.np;
-  const int E = A.E;
-  const float *v = A.v + (size_t)c * E * np + p;
+  const float *v = A.v + (size_t)c * A.E * np + p, *noise = A.noise + p;
   const size_t o = (size_t)c * np + p;
-  int m = 0;
-  float s = 0.0f;
-  for (int e = 0; e < E; ++e) {
-    const float x = v[e * np];
-    if (__builtin_isfinite(x)) {
-      ++m;
-      s = s + x;
-    }
-  }
-  float med = __builtin_nanf("");
-  if (m > 0) {
-    const int klo = (m - 1) / 2, khi = m / 2;
-    unsigned tlo = 0u, thi = 0u;
-    for (int bit = 31; bit >= 0; --bit) {
-      const unsigned clo = tlo | (1u << bit), chi = thi | (1u << bit);
-      int nlo = 0, nhi = 0;
-      for (int e = 0; e < E; ++e) {
-        const float x = v[e * np];
-        if (__builtin_isfinite(x)) {
-          const unsigned k = st_key(x);
-          nlo += k < clo;
-          nhi += k < chi;
-        }
-      }
-      if (nlo <= klo) tlo = clo;
-      if (nhi <= khi) thi = chi;
-    }
-    const float lo = st_unkey(tlo), hi = st_unkey(thi);
-    med = klo == khi ? lo : 0.5f * (lo + hi);
-  }
-  if (A.median) A.median[o] = med;
-  if (!A.stack && !A.nrej) return;
-  const float mean = s / (float)m;
-  float q = 0.0f;
-  for (int e = 0; e < E; ++e) {
-    const float x = v[e * np];
-    if (__builtin_isfinite(x)) {
-      const float d = x - mean;
-      q = q + d * d;
-    }
-  }
-  const float dev = sqrtf(q / (float)m), thr = A.n_sigma * dev;
-  const bool all = !A.clip || !__builtin_isfinite(dev);
-  const float *noise = A.noise + p;
-  float sw = 0.0f, swv = 0.0f;
-  int rej = 0;
-  for (int e = 0; e < E; ++e) {
-    const float x = v[e * np];
-    if (!__builtin_isfinite(x)) continue;
-    if (all || fabsf(x - med) <= thr) {
-      const float w = 1.0f / noise[e * np];
-      sw = sw + w;
-      swv = swv + w * x;
-    } else {
-      ++rej;
-    }
-  }
-  if (A.stack) A.stack[o] = swv / sw;
-  if (A.nrej) A.nrej[o] = rej;
+  const Combined r = robust_combine(
+      A.E, [&](int e) { return float_key_or_missing(v[e * np]); }, [&](int e) { return 1.0f / noise[e * np]; },
+      A.median || A.clip, A.clip, A.n_sigma, !A.stack && !A.nrej);
+  if (A.median) A.median[o] = r.median;
+  if (A.stack) A.stack[o] = r.swv / r.sw;  // NaN by 0 / 0 where no sample is finite
+  if (A.nrej) A.nrej[o] = r.rej;
 }
 
 }  // namespace lc

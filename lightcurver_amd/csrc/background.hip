@@ -145,13 +145,7 @@ __global__ __launch_bounds__(kBgStatThreads) void bg_stats_kernel(BgStatArgs A) 
     unsigned mine = 0;
 #pragma unroll
     for (int i = 0; i < kBgBinsPerLane; ++i) mine += s_hist[tid * kBgBinsPerLane + i];
-    unsigned incl = mine;
-    const int lane = tid & (kWave - 1);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const unsigned up = __shfl_up(incl, o, kWave);
-      if (lane >= o) incl += up;
-    }
+    const unsigned incl = wave_inclusive_scan(mine);
     s_lane[tid] = incl;
     __syncthreads();
     unsigned before = incl - mine;

@@ -1,4 +1,5 @@
-// Workgroup reductions whose order is fixed, for the kernels whose results are compared bit for bit (device only).
+// Workgroup reductions whose order is fixed, for the kernels whose results are compared bit for bit, and the wave scan
+// (device only).
 #pragma once
 #include "lc_common.h"
 
@@ -33,6 +34,18 @@ __device__ __forceinline__ unsigned block_max(unsigned v, unsigned *part) {
   for (int wv = 1; wv < Waves; ++wv) r = max(r, part[wv]);
   __syncthreads();
   return r;
+}
+
+// the inclusive scan of v over the lanes of a wave, returned per lane: lane l holds v of lanes 0 .. l (integers)
+template <class T>
+__device__ __forceinline__ T wave_inclusive_scan(T v) {
+  const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const T up = __shfl_up(v, o, kWave);
+    if (lane >= o) v += up;
+  }
+  return v;
 }
 
 }  // namespace lc

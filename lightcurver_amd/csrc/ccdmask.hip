@@ -14,10 +14,12 @@
 #include <cstring>
 #include <vector>
 
+#include "block_reduce.h"
 #include "cosmics_device.h"
 #include "device_call.h"
 #include "lc_common.h"
 #include "mask_steps.h"
+#include "order_stats.h"
 #include "../../include/lcmi.h"
 
 namespace lc {
@@ -70,15 +72,6 @@ __device__ __forceinline__ float forget_select(float (&v)[kCmKeep], const W &w) 
   } else {
     return v[1];
   }
-}
-
-// order-preserving image of a float in the unsigned integers, and back
-__device__ __forceinline__ unsigned key_of(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned key) {
-  return __uint_as_float((key >> 31) ? (key ^ 0x80000000u) : ~key);
 }
 
 // NumPy's linear interpolation between the order statistics a (rank lo) and b (rank hi)
@@ -150,7 +143,7 @@ __global__ __launch_bounds__(kCmThreads) void ccdmask_kernel(CmArgs A) {
         owner[r] = s_own[r] == r;
       }
       for (int p = tid; p < np; p += kCmThreads) {
-        const unsigned key = key_of(R[p]);
+        const unsigned key = float_key(R[p]);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (owner[r] && (key & high) == pf[r]) atomicAdd(&s_hist[r][(key >> shift) & 255u], 1u);
@@ -163,12 +156,7 @@ __global__ __launch_bounds__(kCmThreads) void ccdmask_kernel(CmArgs A) {
         int want = s_rank[r];
         const int c0 = h[4 * lane], c1 = h[4 * lane + 1], c2 = h[4 * lane + 2], c3 = h[4 * lane + 3];
         const int mine = (c0 + c1) + (c2 + c3);
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int up = __shfl_up(incl, o, 64);
-          if (lane >= o) incl += up;
-        }
+        const int incl = wave_inclusive_scan(mine);
         const int excl = incl - mine;
         if (excl <= want && want < incl) {
           want -= excl;
@@ -192,8 +180,8 @@ __global__ __launch_bounds__(kCmThreads) void ccdmask_kernel(CmArgs A) {
       __syncthreads();
     }
     if (tid == 0) {
-      const float p_lo = interpolate(value_of(s_prefix[0]), value_of(s_prefix[1]), A.t[0]);
-      const float p_hi = interpolate(value_of(s_prefix[2]), value_of(s_prefix[3]), A.t[1]);
+      const float p_lo = interpolate(float_unkey(s_prefix[0]), float_unkey(s_prefix[1]), A.t[0]);
+      const float p_hi = interpolate(float_unkey(s_prefix[2]), float_unkey(s_prefix[3]), A.t[1]);
       s_sigma = (p_hi - p_lo) / 2.0f;
     }
     __syncthreads();

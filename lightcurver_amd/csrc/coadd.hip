@@ -7,8 +7,8 @@
 //            all-taps-inside test in double; weights and the tap sum in float32, y-major.  Writes the samples [n][rows][W]
 //            to scratch, NaN where a tap falls outside the frame.
 //   combine  one lane per output pixel, adjacent lanes adjacent pixels, so every read of a frame's samples is coalesced.
-//            The median is the exact order statistic of stack_kernel (align_stack.hip): bitwise bisection on the
-//            order-preserving integer key, both middle elements at once.  Every sum runs in the order of the list: the
+//            The combine is robust_combine of order_stats.h, which stack_kernel (align_stack.hip) calls too: the median
+//            is the exact order statistic, both middle elements at once.  Every sum runs in the order of the list: the
 //            result depends neither on the launch shape nor on the strip height.  The samples of a pixel are read 35
 //            times (count, 32 bisection steps, deviation, weighted mean): up to kCoLdsFrames frames a wave first copies
 //            the keys of its n x 64 samples to LDS (lane-major: conflict-free) and makes the passes there; beyond that
@@ -22,6 +22,7 @@
 #include "device_call.h"
 #include "frames_state.h"
 #include "lc_common.h"
+#include "order_stats.h"
 #include "resample_device.h"
 #include "../../include/lcmi.h"
 
@@ -66,17 +67,6 @@ struct CoaddCombineArgs {
   int32_t *count, *nrej;
 };
 
-__device__ __forceinline__ unsigned co_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float co_unkey(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-constexpr unsigned kCoMissing = 0xFFFFFFFFu;  // the key of a NaN pattern: of no finite float, and never < a candidate
-__device__ __forceinline__ unsigned co_key_or_missing(float x) { return __builtin_isfinite(x) ? co_key(x) : kCoMissing; }
-
 // LDS: the keys of the wave's samples [n][64] are written to LDS first and every pass reads them there; the passes that
 // need the value take it back from the key, which is exact
 template <bool LDS>
@@ -89,74 +79,14 @@ __global__ __launch_bounds__(LDS ? kCoLdsThreads : kCoThreads) void coadd_combin
   const size_t st = A.stride;
   unsigned *mine = co_lds + threadIdx.x;
   if (LDS)
-    for (int k = 0; k < n; ++k) mine[k * kCoLdsThreads] = co_key_or_missing(v[k * st]);
-  auto key_of = [&](int k) -> unsigned { return LDS ? mine[k * kCoLdsThreads] : co_key_or_missing(v[k * st]); };
-  int m = 0;
-  float s = 0.0f;
-  for (int k = 0; k < n; ++k) {
-    const unsigned key = key_of(k);
-    if (key != kCoMissing) {
-      ++m;
-      s = s + co_unkey(key);
-    }
-  }
-  float img = __builtin_nanf(""), sw = 0.0f;
-  int kept = 0, rej = 0;
-  if (m > 0) {
-    float med = 0.0f;
-    if (A.combine != LC_COADD_MEAN) {
-      const int klo = (m - 1) / 2, khi = m / 2;
-      unsigned tlo = 0u, thi = 0u;
-      for (int bit = 31; bit >= 0; --bit) {
-        const unsigned clo = tlo | (1u << bit), chi = thi | (1u << bit);
-        int nlo = 0, nhi = 0;
-        for (int k = 0; k < n; ++k) {
-          const unsigned key = key_of(k);
-          nlo += key < clo;
-          nhi += key < chi;
-        }
-        if (nlo <= klo) tlo = clo;
-        if (nhi <= khi) thi = chi;
-      }
-      const float lo = co_unkey(tlo), hi = co_unkey(thi);
-      med = klo == khi ? lo : 0.5f * (lo + hi);
-    }
-    bool all = true;
-    float thr = 0.0f;
-    if (A.combine == LC_COADD_SIGMA_CLIP) {
-      const float mean = s / (float)m;
-      float q = 0.0f;
-      for (int k = 0; k < n; ++k) {
-        const unsigned key = key_of(k);
-        if (key != kCoMissing) {
-          const float d = co_unkey(key) - mean;
-          q = q + d * d;
-        }
-      }
-      const float dev = sqrtf(q / (float)m);
-      thr = A.n_sigma * dev;
-      all = !__builtin_isfinite(dev);
-    }
-    float swv = 0.0f;
-    for (int k = 0; k < n; ++k) {
-      const unsigned key = key_of(k);
-      if (key == kCoMissing) continue;
-      const float x = co_unkey(key);
-      if (all || fabsf(x - med) <= thr) {
-        const float w = A.weight[k];
-        sw = sw + w;
-        swv = swv + w * x;
-        ++kept;
-      } else {
-        ++rej;
-      }
-    }
-    img = A.combine == LC_COADD_MEDIAN ? med : swv / sw;
-  }
-  A.image[p] = img;
-  if (A.wsum) A.wsum[p] = sw;
-  if (A.count) A.count[p] = kept;
-  if (A.nrej) A.nrej[p] = rej;
+    for (int k = 0; k < n; ++k) mine[k * kCoLdsThreads] = float_key_or_missing(v[k * st]);
+  const Combined r = robust_combine(
+      n, [&](int k) { return LDS ? mine[k * kCoLdsThreads] : float_key_or_missing(v[k * st]); },
+      [&](int k) { return A.weight[k]; }, A.combine != LC_COADD_MEAN, A.combine == LC_COADD_SIGMA_CLIP, A.n_sigma, false);
+  A.image[p] = r.m == 0 ? __builtin_nanf("") : A.combine == LC_COADD_MEDIAN ? r.median : r.swv / r.sw;
+  if (A.wsum) A.wsum[p] = r.sw;
+  if (A.count) A.count[p] = r.kept;
+  if (A.nrej) A.nrej[p] = r.rej;
 }
 
 }  // namespace lc

@@ -14,8 +14,10 @@
 #include <cstring>
 #include <vector>
 
+#include "block_reduce.h"
 #include "cosmics_device.h"
 #include "device_call.h"
+#include "lacosmic_steps.h"
 #include "lc_common.h"
 #include "../../include/lcmi.h"
 
@@ -42,40 +44,6 @@ struct CrArgs {
   float satg, satg10;   // gain * satlevel, (gain * satlevel) / 10
   float sigclip, sigcliplow, objlim;  // sigcliplow = sigfrac * sigclip
 };
-
-template <int K>
-__device__ __forceinline__ float median_net(float (&v)[K]) {
-#pragma unroll
-  for (int pass = 0; pass < K; ++pass) {
-#pragma unroll
-    for (int i = pass & 1; i + 1 < K; i += 2) {
-      const float a = v[i], b = v[i + 1];
-      v[i] = fminf(a, b);
-      v[i + 1] = fmaxf(a, b);
-    }
-  }
-  return v[K / 2];
-}
-
-// one pass of a separable median: 1 x K along rows (stride 1) or K x 1 along columns (stride n)
-template <int K, bool kRows>
-__device__ __forceinline__ void med_pass(const float *X, float *Y, int n) {
-  constexpr int h = K / 2;
-  const int np = n * n;
-  for (int p = threadIdx.x; p < np; p += kCrThreads) {
-    const int i = p / n, j = p - i * n;
-    const int c = kRows ? j : i;
-    if (c < h || c >= n - h) {
-      Y[p] = X[p];
-    } else {
-      constexpr int s0 = -h;
-      float v[K];
-#pragma unroll
-      for (int t = 0; t < K; ++t) v[t] = X[p + (s0 + t) * (kRows ? 1 : n)];
-      Y[p] = median_net<K>(v);
-    }
-  }
-}
 
 // full k x k median by counting selection (rank (k*k)/2): the sepmed = 0 path, correct rather than fast
 __device__ __forceinline__ void med_full(const float *X, float *Y, int n, int k) {
@@ -104,49 +72,25 @@ __device__ __forceinline__ void med_full(const float *X, float *Y, int n, int k)
   }
 }
 
-// Y = median of X: sepmed -> 1 x k then k x 1 (T is the row pass's output), else the full k_full x k_full median
+// Y = median of X: sepmed -> 1 x KS then KS x 1 (T is the row pass's output), else the full k_full x k_full median
 template <int KS>
 __device__ __forceinline__ void median(bool sepmed, int k_full, const float *X, float *T, float *Y, int n) {
   if (sepmed) {
-    med_pass<KS, true>(X, T, n);
-    __syncthreads();
-    med_pass<KS, false>(T, Y, n);
+    la_sep_median<KS, kCrThreads>(X, T, Y, n, LaRegion{0, 0, n, n});
   } else {
     med_full(X, Y, n, k_full);
+    __syncthreads();
   }
-  __syncthreads();
-}
-
-__device__ __forceinline__ bool dil3_at(const uint8_t *B, int i, int j, int n) {
-  bool r = false;
-  for (int y = max(i - 1, 0); y <= min(i + 1, n - 1); ++y)
-    for (int x = max(j - 1, 0); x <= min(j + 1, n - 1); ++x) r |= B[y * n + x] != 0;
-  return r;
-}
-
-__device__ __forceinline__ float clip0(float v) { return v < 0.f ? 0.f : v; }
-
-// step 2a at pixel (i, j): the four sub-pixels of its 2 x 2 block on the subsampled grid, ring of that grid = 0
-__device__ __forceinline__ float laplace_rebin(const float *C, int i, int j, int n) {
-  const int p = i * n + j;
-  const float c = C[p], c4 = 4.0f * c;
-  const bool top = i == 0, bottom = i == n - 1, left = j == 0, right = j == n - 1;
-  const float up = top ? 0.f : C[p - n], down = bottom ? 0.f : C[p + n];
-  const float lf = left ? 0.f : C[p - 1], rt = right ? 0.f : C[p + 1];
-  const float tl = (top || left) ? 0.f : clip0(c4 - (((up + c) + lf) + c));
-  const float tr = (top || right) ? 0.f : clip0(c4 - (((up + c) + c) + rt));
-  const float bl = (bottom || left) ? 0.f : clip0(c4 - (((c + down) + lf) + c));
-  const float br = (bottom || right) ? 0.f : clip0(c4 - (((c + down) + c) + rt));
-  return ((tl + tr) + (bl + br)) * 0.25f;
 }
 
 template <bool kLds>
 __global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
   extern __shared__ __align__(16) float cr_lds[];
-  __shared__ int s_cnt[kCrThreads / 64];
+  __shared__ int s_cnt[kCrThreads / kWave];
   __shared__ float s_fallback;
   const int n = A.n, np = n * n, tid = threadIdx.x;
   const bool sepmed = A.sepmed != 0;
+  const LaRegion stamp = {0, 0, n, n};  // the region of lacosmic_steps.h is the whole stamp
   float *base = kLds ? cr_lds : A.scratch + (size_t)blockIdx.x * (cr_plane_bytes(n) / 4);
   float *C = base, *Np = C + np, *S = Np + np, *T1 = S + np, *T2 = T1 + np, *Fp = T2 + np;
   uint8_t *M = (uint8_t *)(Fp + np), *CR = M + np, *B1 = CR + np, *B2 = B1 + np;
@@ -155,22 +99,13 @@ __global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
     const size_t off = (size_t)k * np;
     // 0: C = gain D, V = invar gain^2, mask = inmask + the NaN rule
     for (int p = tid; p < np; p += kCrThreads) {
-      const float d = A.data[off + p];
-      float c = A.gain * d;
-      bool hole = !__builtin_isfinite(d);
-      float v = 0.f;
-      if (A.have_invar) {
-        const float iv = A.invar[off + p];
-        hole = hole || !__builtin_isfinite(iv) || iv <= 0.f;
-        v = iv * A.gain2;
-      }
-      if (hole) {
-        c = 0.f;
-        v = A.vhole;
-      }
+      float c, nz;
+      bool m;
+      la_input(A.data[off + p], A.have_invar, A.have_invar ? A.invar[off + p] : 0.f, A.inmask && A.inmask[off + p] != 0,
+               A.gain, A.gain2, A.vhole, &c, &nz, &m);
       C[p] = c;
-      if (A.have_invar) Np[p] = sqrtf(v);
-      M[p] = (hole || (A.inmask && A.inmask[off + p] != 0)) ? 1 : 0;
+      if (A.have_invar) Np[p] = nz;
+      M[p] = m ? 1 : 0;
       CR[p] = 0;
     }
     __syncthreads();
@@ -178,9 +113,9 @@ __global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
     median<7>(sepmed, 5, C, T1, T2, n);
     for (int p = tid; p < np; p += kCrThreads) B1[p] = (C[p] >= A.satg && T2[p] > A.satg10) ? 1 : 0;
     __syncthreads();
-    for (int p = tid; p < np; p += kCrThreads) B2[p] = dil3_at(B1, p / n, p % n, n) ? 1 : 0;
+    for (int p = tid; p < np; p += kCrThreads) B2[p] = la_dil3(B1, p / n, p % n, n) ? 1 : 0;
     __syncthreads();
-    for (int p = tid; p < np; p += kCrThreads) M[p] |= dil3_at(B2, p / n, p % n, n) ? 1 : 0;
+    for (int p = tid; p < np; p += kCrThreads) M[p] |= la_dil3(B2, p / n, p % n, n) ? 1 : 0;
     __syncthreads();
 
     int done = 0;
@@ -195,7 +130,7 @@ __global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
       // a, c: S = L / (2 N), SP = S - m5(S)
       for (int p = tid; p < np; p += kCrThreads) {
         const int i = p / n, j = p - i * n;
-        S[p] = laplace_rebin(C, i, j, n) / (2.0f * Np[p]);
+        S[p] = la_laplace(C, i, j, n, stamp) / (2.0f * Np[p]);
       }
       __syncthreads();
       median<7>(sepmed, 5, S, T1, T2, n);
@@ -212,12 +147,12 @@ __global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
       }
       __syncthreads();
       for (int p = tid; p < np; p += kCrThreads)
-        B2[p] = (dil3_at(B1, p / n, p % n, n) && S[p] > A.sigclip && !M[p]) ? 1 : 0;
+        B2[p] = (la_dil3(B1, p / n, p % n, n) && S[p] > A.sigclip && !M[p]) ? 1 : 0;
       __syncthreads();
       // g: CR |= g2; stop when g2 is empty
       int any = 0;
       for (int p = tid; p < np; p += kCrThreads) {
-        if (dil3_at(B2, p / n, p % n, n) && S[p] > A.sigcliplow && !M[p]) {
+        if (la_dil3(B2, p / n, p % n, n) && S[p] > A.sigcliplow && !M[p]) {
           CR[p] = 1;
           any = 1;
         }
@@ -246,13 +181,8 @@ __global__ __launch_bounds__(kCrThreads) void cosmics_kernel(CrArgs A) {
         // lower median (rank (m - 1) / 2) of the good pixels of the stamp, by counting; 0 when there are none
         int m = 0;
         for (int p = tid; p < np; p += kCrThreads) m += (!CR[p] && !M[p]) ? 1 : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m += __shfl_down(m, o, 64);
-        if ((tid & 63) == 0) s_cnt[tid >> 6] = m;
         if (tid == 0) s_fallback = 0.f;
-        __syncthreads();
-        m = 0;
-        for (int w = 0; w < kCrThreads / 64; ++w) m += s_cnt[w];
+        m = block_sum<kCrThreads / kWave>(m, s_cnt);
         const int r = (m - 1) / 2;
         for (int p = tid; p < np && m > 0; p += kCrThreads) {
           if (CR[p] || M[p]) continue;

@@ -27,8 +27,10 @@
 #include "cosmics_frames_device.h"
 #include "device_call.h"
 #include "frames_state.h"
+#include "lacosmic_steps.h"
 #include "lc_common.h"
 #include "noise_pixel.h"
+#include "order_stats.h"
 #include "../../include/lcmi.h"
 
 namespace lc {
@@ -72,81 +74,13 @@ struct CfArgs {
   float sigclip, sigcliplow, objlim;  // sigcliplow = sigfrac * sigclip
 };
 
-// the region of a workgroup: LDS pixel (ly, lx) is frame pixel (oy + ly, ox + lx)
-struct CfTile {
-  int oy, ox, h, w;
-  __device__ __forceinline__ bool inside(int ly, int lx) const {
-    const int gy = oy + ly, gx = ox + lx;
-    return gy >= 0 && gy < h && gx >= 0 && gx < w;
-  }
-};
+// the region of a workgroup (lacosmic_steps.h): LDS pixel (ly, lx) is frame pixel (oy + ly, ox + lx)
+using CfTile = LaRegion;
 
-template <int K>
-__device__ __forceinline__ float cf_median_net(float (&v)[K]) {
-#pragma unroll
-  for (int pass = 0; pass < K; ++pass) {
-#pragma unroll
-    for (int i = pass & 1; i + 1 < K; i += 2) {
-      const float a = v[i], b = v[i + 1];
-      v[i] = fminf(a, b);
-      v[i + 1] = fmaxf(a, b);
-    }
-  }
-  return v[K / 2];
-}
-
-// One pass of a separable median over the region.  The (K - 1) / 2 pixels at the FRAME's edge keep the input; so does a
-// pixel whose window leaves the region: it lies in the halo, farther out than anything the tile's result reads.
-template <int K, bool kRows>
-__device__ __forceinline__ void cf_med_pass(const float *X, float *Y, const CfTile &T) {
-  constexpr int hh = K / 2;
-  for (int p = threadIdx.x; p < kCfNp; p += kCfThreads) {
-    const int ly = p / kCfR, lx = p - ly * kCfR;
-    const int cl = kRows ? lx : ly;
-    const int cf = (kRows ? T.ox : T.oy) + cl, nf = kRows ? T.w : T.h;
-    float out = X[p];
-    if (cf >= hh && cf < nf - hh && cl >= hh && cl < kCfR - hh) {
-      float v[K];
-#pragma unroll
-      for (int t = 0; t < K; ++t) v[t] = X[p + (t - hh) * (kRows ? 1 : kCfR)];
-      out = cf_median_net<K>(v);
-    }
-    Y[p] = out;
-  }
-}
-
-// Y = 1 x K median along rows, then K x 1 along columns (T1 is the row pass's output)
+// Y = the separable K median of X over the region (T1 is the row pass's output)
 template <int K>
 __device__ __forceinline__ void cf_median(const float *X, float *T1, float *Y, const CfTile &T) {
-  cf_med_pass<K, true>(X, T1, T);
-  __syncthreads();
-  cf_med_pass<K, false>(T1, Y, T);
-  __syncthreads();
-}
-
-// 3 x 3 dilation; B is 0 outside the frame, which clips it there
-__device__ __forceinline__ bool cf_dil3(const uint8_t *B, int ly, int lx) {
-  bool r = false;
-  for (int y = max(ly - 1, 0); y <= min(ly + 1, kCfR - 1); ++y)
-    for (int x = max(lx - 1, 0); x <= min(lx + 1, kCfR - 1); ++x) r |= B[y * kCfR + x] != 0;
-  return r;
-}
-
-__device__ __forceinline__ float cf_clip0(float v) { return v < 0.f ? 0.f : v; }
-
-// step 2a at region pixel p = (ly, lx): as laplace_rebin of cosmics.hip, the ring of the 2x grid being the frame's
-__device__ __forceinline__ float cf_laplace(const float *C, int ly, int lx, const CfTile &T) {
-  const int p = ly * kCfR + lx, gy = T.oy + ly, gx = T.ox + lx;
-  const float c = C[p], c4 = 4.0f * c;
-  const bool top = gy <= 0, bottom = gy >= T.h - 1, left = gx <= 0, right = gx >= T.w - 1;
-  // (at the region's edge, inside the frame, the neighbour is not in LDS: such a pixel lies in the halo's outer ring)
-  const float up = (top || ly == 0) ? 0.f : C[p - kCfR], down = (bottom || ly == kCfR - 1) ? 0.f : C[p + kCfR];
-  const float lf = (left || lx == 0) ? 0.f : C[p - 1], rt = (right || lx == kCfR - 1) ? 0.f : C[p + 1];
-  const float tl = (top || left) ? 0.f : cf_clip0(c4 - (((up + c) + lf) + c));
-  const float tr = (top || right) ? 0.f : cf_clip0(c4 - (((up + c) + c) + rt));
-  const float bl = (bottom || left) ? 0.f : cf_clip0(c4 - (((c + down) + lf) + c));
-  const float br = (bottom || right) ? 0.f : cf_clip0(c4 - (((c + down) + c) + rt));
-  return ((tl + tr) + (bl + br)) * 0.25f;
+  la_sep_median<K, kCfThreads>(X, T1, Y, kCfR, T);
 }
 
 __device__ __forceinline__ CfTile cf_tile(const CfArgs &A) {
@@ -158,28 +92,16 @@ __device__ __forceinline__ CfTile cf_tile(const CfArgs &A) {
 __device__ __forceinline__ void cf_input(const CfArgs &A, int k, size_t q, float *c_out, float *n_out, bool *m_out) {
   const int plane = A.frame ? A.frame[k] : k;
   const float d = A.data[(size_t)plane * A.hw + q];
-  float c = A.gain * d;
-  bool hole = !__builtin_isfinite(d);
-  float v = 0.f;
-  if (A.have_var) {
-    float iv;
-    if (A.invar) {
-      iv = A.invar[(size_t)k * A.hw + q];
-    } else {
-      const float t = A.exptime[plane];
-      const float e = noise_from_rms(d, t, noise_trms2(t, A.rms[plane]));
-      iv = e * e;
-    }
-    hole = hole || !__builtin_isfinite(iv) || iv <= 0.f;
-    v = iv * A.gain2;
+  float iv = 0.f;
+  if (A.invar) {
+    iv = A.invar[(size_t)k * A.hw + q];
+  } else if (A.have_var) {
+    const float t = A.exptime[plane];
+    const float e = noise_from_rms(d, t, noise_trms2(t, A.rms[plane]));
+    iv = e * e;
   }
-  if (hole) {
-    c = 0.f;
-    v = A.vhole;
-  }
-  *c_out = c;
-  *n_out = A.have_var ? sqrtf(v) : 0.f;
-  *m_out = hole || (A.inmask && A.inmask[(size_t)k * A.hw + q] != 0);
+  la_input(d, A.have_var, iv, A.inmask && A.inmask[(size_t)k * A.hw + q] != 0, A.gain, A.gain2, A.vhole, c_out, n_out,
+           m_out);
 }
 
 // steps 0 and 1 of a tile; grid (tiles, frames of the chunk)
@@ -207,7 +129,7 @@ __global__ __launch_bounds__(kCfThreads) void cf_prep_kernel(CfArgs A) {
   __syncthreads();
   for (int p = tid; p < kCfNp; p += kCfThreads) {
     const int ly = p / kCfR, lx = p - ly * kCfR;
-    B2[p] = (T.inside(ly, lx) && cf_dil3(B1, ly, lx)) ? 1 : 0;
+    B2[p] = (T.inside(ly, lx) && la_dil3(B1, ly, lx, kCfR)) ? 1 : 0;
   }
   __syncthreads();
   const size_t base = (size_t)k * A.hw;
@@ -218,7 +140,7 @@ __global__ __launch_bounds__(kCfThreads) void cf_prep_kernel(CfArgs A) {
     const size_t q = base + (size_t)(T.oy + ly) * A.w + (T.ox + lx);
     A.C[q] = C[r];
     if (A.have_var) A.N[q] = Np[r];
-    A.M[q] = (M[r] || cf_dil3(B2, ly, lx)) ? 1 : 0;
+    A.M[q] = (M[r] || la_dil3(B2, ly, lx, kCfR)) ? 1 : 0;
     A.CR[q] = 0;
   }
 }
@@ -257,7 +179,7 @@ __global__ __launch_bounds__(kCfThreads) void cf_detect_kernel(CfArgs A) {
   // a, c: S = L / (2 N), SP = S - m5(S)
   for (int p = tid; p < kCfNp; p += kCfThreads) {
     const int ly = p / kCfR, lx = p - ly * kCfR;
-    S[p] = cf_laplace(C, ly, lx, T) / (2.0f * Np[p]);
+    S[p] = la_laplace(C, ly, lx, kCfR, T) / (2.0f * Np[p]);
   }
   __syncthreads();
   cf_median<7>(S, T1, T2, T);
@@ -275,7 +197,7 @@ __global__ __launch_bounds__(kCfThreads) void cf_detect_kernel(CfArgs A) {
   __syncthreads();
   for (int p = tid; p < kCfNp; p += kCfThreads) {
     const int ly = p / kCfR, lx = p - ly * kCfR;
-    B2[p] = (cf_dil3(B1, ly, lx) && S[p] > A.sigclip && !M[p]) ? 1 : 0;
+    B2[p] = (la_dil3(B1, ly, lx, kCfR) && S[p] > A.sigclip && !M[p]) ? 1 : 0;
   }
   __syncthreads();
   // g: CR |= g2 on the tile
@@ -284,7 +206,7 @@ __global__ __launch_bounds__(kCfThreads) void cf_detect_kernel(CfArgs A) {
     const int ly = kCfHalo + p / kCfTile, lx = kCfHalo + p % kCfTile;
     if (!T.inside(ly, lx)) continue;
     const int r = ly * kCfR + lx;
-    if (cf_dil3(B2, ly, lx) && S[r] > A.sigcliplow && !M[r]) {
+    if (la_dil3(B2, ly, lx, kCfR) && S[r] > A.sigcliplow && !M[r]) {
       A.CR[base + (size_t)(T.oy + ly) * A.w + (T.ox + lx)] = 1;
       any = 1;
     }
@@ -328,14 +250,6 @@ __global__ __launch_bounds__(kCfPixThreads) void cf_clean_kernel(CfArgs A) {
   if (__syncthreads_or(need) && threadIdx.x == 0) atomicOr(&st[kStNeed], 1);
 }
 
-__device__ __forceinline__ unsigned cf_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float cf_unkey(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 __device__ __forceinline__ bool cf_selecting(const int32_t *st) { return cf_cleaning(st) && st[kStNeed]; }
 
 // pass A.pass of the radix select: the histogram of byte 3 - pass of the keys of the good pixels whose higher bytes
@@ -352,7 +266,7 @@ __global__ __launch_bounds__(kCfPixThreads) void cf_hist_kernel(CfArgs A) {
   __syncthreads();
   for (size_t p = (size_t)blockIdx.x * kCfPixThreads + threadIdx.x; p < A.hw; p += (size_t)gridDim.x * kCfPixThreads) {
     if (A.CR[base + p] || A.M[base + p]) continue;
-    const unsigned key = cf_key(A.C[base + p]);
+    const unsigned key = float_key(A.C[base + p]);
     if (A.pass > 0 && (key >> (shift + 8)) != (prefix >> (shift + 8))) continue;
     atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
   }
@@ -387,7 +301,7 @@ __global__ __launch_bounds__(64) void cf_pick_kernel(CfArgs A, int frames) {
     const unsigned prefix = (unsigned)st[kStPrefix] | ((unsigned)b << (24 - 8 * A.pass));
     st[kStPrefix] = (int)prefix;
     st[kStRank] = rank - (int)cum;
-    if (A.pass == 3) st[kStFallback] = (int)__float_as_uint(cf_unkey(prefix));
+    if (A.pass == 3) st[kStFallback] = (int)__float_as_uint(float_unkey(prefix));
   }
   for (int b = 0; b < 256; ++b) hist[b] = 0;
 }

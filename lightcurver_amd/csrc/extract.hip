@@ -348,12 +348,7 @@ __global__ __launch_bounds__(kExThreads) void ex_scan_kernel(ExNumberArgs A) {
   for (unsigned c0 = 0; c0 < A.g.nblk; c0 += kExThreads) {
     const unsigned i = c0 + tid;
     const int v = i < A.g.nblk ? blk[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int up = __shfl_up(incl, o, kWave);
-      if (lane >= o) incl += up;
-    }
+    const int incl = wave_inclusive_scan(v);
     if (lane == kWave - 1) s_wave[wv] = incl;
     __syncthreads();
     int before = 0, total = 0;

@@ -2475,13 +2475,13 @@ int lc_joint_run_lbfgs(lc_joint *j, int maxiter, const float *const lower[LC_P_C
   // device work space (freed on every exit path)
   float *buf = nullptr;
   int *order_dev = nullptr;
-  const size_t nvec = 7 + 2 * (size_t)kLbMem;
+  const size_t nvec = 7 + 2 * (size_t)kLbRing;
   DevPool scratch;
-  LC_HIP(j->ctx, scratch.alloc(nvec * D + kLbMem + 8, &buf));
+  LC_HIP(j->ctx, scratch.alloc(nvec * D + kLbRing + 8, &buf));
   LC_HIP(j->ctx, scratch.alloc((size_t)kLbMem, &order_dev));
   // hipMalloc hands back recycled bytes: nothing below reads a vector before writing it, and the work space starts from
   // zeros all the same (LCMI_LBFGS_POISON, a test hook, fills it with NaN patterns instead: the results must not change)
-  LC_HIP(j->ctx, hipMemsetAsync(buf, std::getenv("LCMI_LBFGS_POISON") ? 0xFF : 0, (nvec * D + kLbMem + 8) * sizeof(float), q));
+  LC_HIP(j->ctx, hipMemsetAsync(buf, std::getenv("LCMI_LBFGS_POISON") ? 0xFF : 0, (nvec * D + kLbRing + 8) * sizeof(float), q));
   LC_HIP(j->ctx, hipMemsetAsync(order_dev, 0, kLbMem * sizeof(int), q));
   LbfgsDev L;
   L.D = D;
@@ -2494,9 +2494,9 @@ int lc_joint_run_lbfgs(lc_joint *j, int maxiter, const float *const lower[LC_P_C
   L.lo = dlo;
   L.hi = dhi;
   L.S = buf + 7 * (size_t)D;
-  L.Y = L.S + (size_t)kLbMem * D;
-  L.rho = L.Y + (size_t)kLbMem * D;
-  L.scal = L.rho + kLbMem;
+  L.Y = L.S + (size_t)kLbRing * D;
+  L.rho = L.Y + (size_t)kLbRing * D;
+  L.scal = L.rho + kLbRing;
   LC_HIP(j->ctx, hipMemcpyAsync(dlo, lo.data(), (size_t)D * sizeof(float), hipMemcpyHostToDevice, q));
   LC_HIP(j->ctx, hipMemcpyAsync(dhi, hi.data(), (size_t)D * sizeof(float), hipMemcpyHostToDevice, q));
   auto pack = [&](float *const src[LC_P_COUNT], float *vec) -> int {   // parameter blocks -> flat vector
@@ -2540,12 +2540,12 @@ int lc_joint_run_lbfgs(lc_joint *j, int maxiter, const float *const lower[LC_P_C
     if (loss_history && n_hist < history_capacity) loss_history[n_hist] = v;
     ++n_hist;
   };
-  int m = 0, head = 0, iters = 0;  // m pairs stored, next slot = head
+  int m = 0, head = 0, iters = 0;  // m <= kLbMem pairs stored in the kLbRing slots before `head`; next pair -> slot head
   const float c1 = 1e-4f, gtol = 1e-6f, ftol = 2.2e-9f;
   bool finite = std::isfinite(f);
   while (finite && iters < maxiter) {
     int order[kLbMem];
-    for (int k = 0; k < m; ++k) order[k] = (head - m + k + 2 * kLbMem) % kLbMem;  // oldest .. newest
+    for (int k = 0; k < m; ++k) order[k] = (head - m + k + kLbRing) % kLbRing;  // oldest .. newest
     LC_HIP(j->ctx, hipMemcpyAsync(order_dev, order, sizeof(order), hipMemcpyHostToDevice, q));
     hipLaunchKernelGGL(lb_direction_kernel, dim3(1), dim3(kLbThreads), 0, q, L, m, order_dev);
     LC_HIP(j->ctx, hipMemcpyAsync(host, L.scal, 3 * sizeof(float), hipMemcpyDeviceToHost, q));
@@ -2586,8 +2586,8 @@ int lc_joint_run_lbfgs(lc_joint *j, int maxiter, const float *const lower[LC_P_C
     LC_HIP(j->ctx, hipMemcpyAsync(host, L.scal + 4, 3 * sizeof(float), hipMemcpyDeviceToHost, q));
     LC_HIP(j->ctx, hipStreamSynchronize(q));
     const float sy = host[0], ss = host[1], yy = host[2];
-    if (sy > 1e-10f * std::sqrt(ss * yy) && sy > 0.f) {  // keep the pair (the slot was written by the kernel)
-      head = (head + 1) % kLbMem;
+    if (sy > 1e-10f * std::sqrt(ss * yy) && sy > 0.f) {  // keep the pair (the kernel wrote it into the spare slot)
+      head = (head + 1) % kLbRing;
       m = std::min(m + 1, kLbMem);
     }
     const float fold = f;

@@ -13,13 +13,15 @@ namespace lc {
 
 constexpr int kLbThreads = 1024;
 constexpr int kLbMem = 10;
+constexpr int kLbRing = kLbMem + 1;  // slots of the ring: the accept kernel writes a pair before the host has judged it, into
+                                     // the spare slot, so a pair that fails the curvature guard costs no stored pair
 
 struct LbfgsDev {
   int D;
   float *x, *g, *xt, *gt, *dir;   // [D]
   const float *lo, *hi;           // [D]
-  float *S, *Y;                   // [kLbMem][D] ring buffers
-  float *rho;                     // [kLbMem]
+  float *S, *Y;                   // [kLbRing][D] ring buffers
+  float *rho;                     // [kLbRing]
   float *scal;                    // [8] results for the host
 };
 

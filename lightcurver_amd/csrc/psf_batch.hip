@@ -296,7 +296,11 @@ int launch_psf(lc_psf_batch *b, int mode, int n_iter, const lc_adabelief_cfg *cf
   const int split_grid = ((b->F + 7) / 8) * 16;
   // (not for launches of a few iterations - the step-by-step drive of the distortion fit: the copies of the pre-launch state
   // the fall-back needs cost ~35 us per launch, the two-workgroup form gains ~9 us per iteration)
-  bool split = mode == 1 && n_iter >= 4 && v->fn_split && (A.lam_sc != 0.f || A.lam_hf != 0.f) && !std::getenv("LCMI_PSF_SINGLE_WG");
+  // The two-workgroup kernel is compiled for exactly this launch (psf_kernels.h, LOOP_ONLY): it takes mode == 1, null eval
+  // outputs, a non-zero regulariser weight and heal == 0 as facts and tests none of them.  Every term below that states one of
+  // them is therefore part of the kernel's contract, not only a matter of speed; anything else goes to the one-workgroup form.
+  bool split = mode == 1 && !want_outputs && n_iter >= 4 && v->fn_split && (A.lam_sc != 0.f || A.lam_hf != 0.f) &&
+               !std::getenv("LCMI_PSF_SINGLE_WG");
   if (split) {
     LC_HIP(b->ctx, hipFuncSetAttribute((const void *)v->fn_split, hipFuncAttributeMaxDynamicSharedMemorySize, v->lds_bytes));
     if (b->split_blocks_per_cu < 0) {

@@ -39,6 +39,15 @@
 #ifndef LC_V_ZERO_ONCE
 #define LC_V_ZERO_ONCE LC_TASK_AHEAD  // C2, two workgroups: role 0 writes the zero columns of V once per launch, not in every edge task
 #endif
+// DESIGN.md, "PSF fit: the two-workgroup loop without its launch constants"
+// (make alt ALTFLAGS="-DLC_LOOP_ONLY=0 -DLC_LOOP_TOP_LIVE=0" for the kernel before it, -DLC_LOOP_TOP_LIVE=0 for the first item alone;
+// the second does nothing without the first, whose registers it spends)
+#ifndef LC_LOOP_ONLY
+#define LC_LOOP_ONLY 1  // two workgroups: mode == 1, no eval outputs and a regulariser are facts of the launch, not tests in the loop
+#endif
+#ifndef LC_LOOP_TOP_LIVE
+#define LC_LOOP_TOP_LIVE 1  // C2, two workgroups: role 0 keeps its own addresses live across the loop top
+#endif
 namespace lc {
 constexpr int kXFlagStride = 16;   // flag words per (frame, role): word 0 is the flag, the rest keeps (frame, role) pairs on lines of their own
 
@@ -132,6 +141,11 @@ struct PsfCfg {
   // WC: the row pass, column pass and transposed column pass of one (star, block of JB down-sampled columns)
   // run inside ONE wave with wave-level synchronisation only (per-wave LDS scratch)
   static constexpr bool WC = WC_;
+  // SPLIT_LOOP_ONLY: the two-workgroup kernel of this configuration is compiled for the one launch it gets (LOOP_ONLY in
+  // psf_fit_kernel).  Not N = 48 and N = 128, and for a reason outside the kernels: with it they come out with fewer registers
+  // (157 for 164; 32 spilled for 36), and tests/test_psf_budget_isa_cpu.py holds every kernel but N = 32 and N = 64 to the exact
+  // figures of its recorded table.  When that table is recorded anew this becomes `true` for every configuration.
+  static constexpr bool SPLIT_LOOP_ONLY = (N == 32 || N == 64);
   static constexpr int n = N / SS;
   static constexpr int NTHR = N * N / PX;
   static constexpr int NW = (NTHR + kWave - 1) / kWave;
@@ -289,6 +303,13 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
   int same_xcd = 0;
   const int tid0 = threadIdx.x;
   const int S = A.S;
+  // The host launches the two-workgroup form only for the optimisation loop (launch_psf, psf_batch.hip: `split`): mode == 1, all
+  // six eval outputs null, at least one regulariser weight non-zero, heal == 0.  LOOP_ONLY compiles those facts in, so that the
+  // hot loop of that form tests none of them; ext_grad and force_abort_it stay what they are, per-launch inputs.  The
+  // one-workgroup form keeps every test: it serves evaluate(), the outputs, short launches and the heal launch.
+  // (Which configurations: PsfCfg::SPLIT_LOOP_ONLY.)
+  constexpr bool LOOP_ONLY = SPLIT && LC_LOOP_ONLY && C::SPLIT_LOOP_ONLY;
+  const bool loop = LOOP_ONLY || A.mode == 1;
 
   const float *dataf = A.data + (size_t)f * S * n * n;
   const float *wgtf = A.wgt + (size_t)f * S * n * n;
@@ -419,6 +440,12 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
   //   pipelined stretch is one basic block only without them (measured: either alone gains about one run-to-run spread, the pair four).
   constexpr bool C2_SPLIT = SPLIT && C::WC && PX == 8;
   constexpr bool TASK_AHEAD = C2_SPLIT && LC_TASK_AHEAD, V_ZERO_ONCE = C2_SPLIT && LC_V_ZERO_ONCE;
+  // The same kernel's loop top ("PSF fit: the two-workgroup loop without its launch constants"): role 0 derives what
+  // it addresses by - its row and columns, its lane and wave, the wave's tiles - from the thread index itself, not from the
+  // laundered copy, so the compiler is free to keep them across iterations; role 1 and the code both roles run keep the
+  // laundered index.  The registers are those LOOP_ONLY frees (252 of 256 with both; without LOOP_ONLY five would be spilled,
+  // so the second switch does nothing without the first).
+  constexpr bool TOP_LIVE = C2_SPLIT && LOOP_ONLY && LC_LOOP_TOP_LIVE;
   if constexpr (V_ZERO_ONCE) {
     if (role == 0) {
       for (int i = tid0; i < SG * N; i += NTHR) {
@@ -454,13 +481,17 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     const int pu = tid / (N / PX);         // owned row
     const int pv = (tid % (N / PX)) * PX;  // first owned column
     const size_t gpix = (size_t)f * N * N + (size_t)pu * N + pv;
-    if (tid < 3 && A.mode == 1) SCAL[tid] = A.sched[3 * tglob + tid];  // lr, bc1, bc2
+    // (role 0's own: the same values, TOP_LIVE from the index that is not laundered)
+    const int tid_c = TOP_LIVE ? tid0 : tid, lane_c = tid_c & 63, wid_c = tid_c >> 6;
+    const int pu_c = tid_c / (N / PX), pv_c = (tid_c % (N / PX)) * PX;
+    if (tid < 3 && loop) SCAL[tid] = A.sched[3 * tglob + tid];  // lr, bc1, bc2
     LC_STAMP(0);
     float gB[PX];
 #pragma unroll
     for (int p = 0; p < PX; ++p) gB[p] = 0.f;
     float tpix[PX];  // T at the thread's own pixels (WC layout)
     if (conv_role) {
+    // (role 0 and the one-workgroup form: everything in this block goes by tid_c, lane_c, wid_c, pu_c, pv_c)
     // ---- P1: T = Moffat + B into LDS -----------------------------------------------------
     if constexpr (TRIM) {  // (written behind the pixel step of the iteration before, or in front of the loop)
 #pragma unroll
@@ -469,24 +500,28 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
 #pragma unroll
       for (int p = 0; p < PX; ++p) {
         tpix[p] = Bp[p] + Tp[p];
-        T[pu * C::TSA + C::AP + pv + p] = tpix[p];
+        T[pu_c * C::TSA + C::AP + pv_c + p] = tpix[p];
       }
     } else if (STATE_REGS) {
 #pragma unroll
-      for (int p = 0; p < PX; ++p) T[pu * TS + pv + p] = Bp[p] + Tp[p];
+      for (int p = 0; p < PX; ++p) T[pu_c * TS + pv_c + p] = Bp[p] + Tp[p];
     } else {
       const float4 *bp = (const float4 *)(Bg + gpix);
       const float4 *tp = (const float4 *)(A.Tm + gpix);
 #pragma unroll
       for (int q = 0; q < PX / 4; ++q) {
         const float4 b = bp[q], t = tp[q];
-        T[pu * TS + pv + 4 * q + 0] = b.x + t.x;
-        T[pu * TS + pv + 4 * q + 1] = b.y + t.y;
-        T[pu * TS + pv + 4 * q + 2] = b.z + t.z;
-        T[pu * TS + pv + 4 * q + 3] = b.w + t.w;
+        T[pu_c * TS + pv_c + 4 * q + 0] = b.x + t.x;
+        T[pu_c * TS + pv_c + 4 * q + 1] = b.y + t.y;
+        T[pu_c * TS + pv_c + 4 * q + 2] = b.z + t.z;
+        T[pu_c * TS + pv_c + 4 * q + 3] = b.w + t.w;
       }
     }
-    if (tid < S * 5) SGR[tid] = 0.f;
+    // (TOP_LIVE: not zeroed.  Every slot a star < S has is assigned, not added to, before its first reader of the iteration:
+    //  slots 0, 1, 3, 4 behind the barrier that ends the wave tasks, slot 2 behind the barrier that follows P5; the stars' step,
+    //  the loss and out_gstars read behind those.  No reader ever sees the zero.)
+    if constexpr (!TOP_LIVE)
+      if (tid_c < S * 5) SGR[tid_c] = 0.f;
     // (the tap tables of this iteration were made at the end of the previous one, behind the star update: compute_taps)
 
     for (int g0 = 0; g0 < S; g0 += SG) {
@@ -497,7 +532,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       if constexpr (C::WC) {
         // ---- wave tasks: (star, block of JB down-sampled columns), everything up to V inside the wave ----
         constexpr int JB = C::JB, NBLK = n / JB;
-        float *wsc = lds + C::OFF_WSC + wid * C::WSZ;
+        float *wsc = lds + C::OFF_WSC + wid_c * C::WSZ;
         constexpr int TSA = C::TSA, AP = C::AP, APR = C::APR;
         float *R2w = wsc + AP, *RESw = wsc + JB * TSA + APR * C::JBP;
         // (Two waves share a SIMD and the arbiter favours the older one: waves 0-3 are done after ~14 k cycles, waves 4-7
@@ -520,7 +555,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           //   neither RESw nor V, the transposed pass touches nothing else.
           static_assert(SS == 2 && N == kWave && JB * (n / LC) == kWave && LA == LC, "one item per lane in each pass of a task");
           constexpr int NP = (NT + 1) / 2, WL2 = (JB - 1) + NP, WL = SS * (LC - 1) + NT, WI = (SS * LA - 1 + NT - 1) / SS + 1;
-          const int jl = lane % JB, a0 = (lane / JB) * LC;  // column pass and transposed pass: the lane's column and first data row
+          const int jl = lane_c % JB, a0 = (lane_c / JB) * LC;  // column pass and transposed pass: the lane's column and first data row
           // (tasks of stars >= S are skipped, wave-uniform: they are the last ones, tasks are ordered by star)
           const int ntask = min(SG, S - g0) * NBLK;
           float dpre[LC], wpre[LC];        // data / weights of the task whose row pass ran last
@@ -542,7 +577,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
             const float *tx = TAPS + (s * 4 + 0) * NTP;
 #pragma unroll
             for (int h = 0; h < NP; ++h) tr2[h] = (lc_v2f){tx[NT - 1 - 2 * h], tx[NT - 2 - 2 * h]};  // tx[-1] = 0
-            const float *trow = T + lane * TSA + AP + SS * (jd0 - bqx) - (NT - 1);
+            const float *trow = T + lane_c * TSA + AP + SS * (jd0 - bqx) - (NT - 1);
 #pragma unroll
             for (int i = 0; i < WL2; ++i) win2[i] = (lc_v2f){trow[2 * i], trow[2 * i + 1]};
           };
@@ -556,7 +591,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               for (int j = 0; j < JB; ++j) acc[j] = pk_fma(tr2[h], win2[j + h], acc[j]);
             }
 #pragma unroll
-            for (int j = 0; j < JB; ++j) R2w[j * TSA + lane] = acc[j].x + acc[j].y;
+            for (int j = 0; j < JB; ++j) R2w[j * TSA + lane_c] = acc[j].x + acc[j].y;
           };
           // transposed column pass, lane = (column, strip of high-res rows): as in the loop below
           auto tcol_request = [&](int task, int bqy) {
@@ -598,7 +633,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           };
           // kdone: tasks this wave has finished - the wave that is behind gets the issue priority.  (The task index is the same in
           // every lane; said so, the loop's branches and the tasks' star and block indices are scalar.)
-          int task = __builtin_amdgcn_readfirstlane(wid), kdone = 0;
+          int task = __builtin_amdgcn_readfirstlane(wid_c), kdone = 0;
           int bqy = 0;
           if (task < ntask) {
             progress_prio(0);
@@ -651,12 +686,13 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
                 lgy = fmaf(rw, fy, lgy);
                 gs += rw;
                 RESw[(a0 + j) * C::JBP + jl] = rw;
-                if (A.out_model) A.out_model[(size_t)f * S * n * n + (size_t)s * n * n + (size_t)(a0 + j) * n + jd0 + jl] = model;
+                if constexpr (!LOOP_ONLY)
+                  if (A.out_model) A.out_model[(size_t)f * S * n * n + (size_t)s * n * n + (size_t)(a0 + j) * n + jd0 + jl] = model;
               }
               gy += lgy * amp * SS;
             }
             wave_sum4(chi, ga, gy, gs);
-            if (lane == 0) {
+            if (lane_c == 0) {
               float *r = RED + (s * NBLK + blk) * 5;
               r[0] = chi;
               r[1] = ga;
@@ -688,7 +724,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           }
         } else {
         int kdone = 0;  // tasks this wave has finished: the wave that is behind gets the issue priority (progress_prio)
-        for (int task = wid; task < SG * NBLK; task += C::NW, ++kdone) {
+        for (int task = wid_c; task < SG * NBLK; task += C::NW, ++kdone) {
           progress_prio(kdone);
           const int sl = task / NBLK, blk = task % NBLK, s = g0 + sl;
           if (s >= S) continue;  // wave-uniform
@@ -702,7 +738,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           float dpre[NI3][LC], wpre[NI3][LC];
 #pragma unroll
           for (int i3 = 0; i3 < NI3; ++i3) {
-            const int item = lane + 64 * i3;
+            const int item = lane_c + 64 * i3;
             const bool ok = item < JB * (n / LC);
             const int jl = item % JB, a0 = (item / JB) * LC;
 #pragma unroll
@@ -726,7 +762,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               lc_v2f tr2[NP];
 #pragma unroll
               for (int h = 0; h < NP; ++h) tr2[h] = (lc_v2f){tx[NT - 1 - 2 * h], tx[NT - 2 - 2 * h]};  // tx[-1] = 0
-              for (int u = lane; u < N; u += 64) {
+              for (int u = lane_c; u < N; u += 64) {
                 lc_v2f win2[WL2];
                 const float *trow = T + u * TSA + AP + ws;
 #pragma unroll
@@ -749,7 +785,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               float tk[NT];
 #pragma unroll
               for (int k = 0; k < NT; ++k) tk[k] = tx[k];
-              for (int u = lane; u < N; u += 64) {
+              for (int u = lane_c; u < N; u += 64) {
                 float win[WL];
                 const float *trow = T + u * TSA + AP + ws;
 #pragma unroll
@@ -776,7 +812,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
             for (int k = 0; k < NT; ++k) tyd[k] = TAPP[(s * 2 + 1) * NT + k];
 #pragma unroll
             for (int i3 = 0; i3 < NI3; ++i3) {
-              const int item = lane + 64 * i3;
+              const int item = lane_c + 64 * i3;
               if (item < JB * (n / LC)) {
                 const int jl = item % JB, a0 = (item / JB) * LC;
                 const int ws = SS * (a0 - bqy) - (NT - 1);
@@ -807,14 +843,15 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
                   lgy = fmaf(rw, fy, lgy);
                   gs += rw;
                   RESw[(a0 + j) * C::JBP + jl] = rw;
-                  if (A.out_model) A.out_model[(size_t)f * S * n * n + (size_t)s * n * n + (size_t)(a0 + j) * n + jd0 + jl] = model;
+                  if constexpr (!LOOP_ONLY)
+                    if (A.out_model) A.out_model[(size_t)f * S * n * n + (size_t)s * n * n + (size_t)(a0 + j) * n + jd0 + jl] = model;
                 }
                 gy += lgy * amp * SS;
               }
             }
           }
           wave_sum4(chi, ga, gy, gs);
-          if (lane == 0) {
+          if (lane_c == 0) {
             float *r = RED + (s * NBLK + blk) * 5;
             r[0] = chi;
             r[1] = ga;
@@ -835,7 +872,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               for (int q = 0; q < NP; ++q) py[q] = (lc_v2f){ty[2 * q], ty[2 * q - 1]};  // ty[-1] = ty[NT] = 0
 #pragma unroll
               for (int i4 = 0; i4 < NI4; ++i4) {
-                const int item = lane + 64 * i4;
+                const int item = lane_c + 64 * i4;
                 if (item < JB * (n / LA)) {
                   const int jl = item % JB, a0 = (item / JB) * LA;
                   lc_v2f out2[LA];
@@ -875,7 +912,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               for (int k = 0; k < NT; ++k) tk[k] = ty[k];
 #pragma unroll
               for (int i4 = 0; i4 < NI4; ++i4) {
-                const int item = lane + 64 * i4;
+                const int item = lane_c + 64 * i4;
                 if (item < JB * (n / LA)) {
                   const int jl = item % JB, a0 = (item / JB) * LA;
                   float out[SS * LA];
@@ -912,12 +949,12 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         __builtin_amdgcn_s_setprio(0);
         LC_STAMP(14);
 #ifdef LC_STAMPS
-        if (blockIdx.x == 0 && lane == 0 && it == A.n_iter - 1) g_stamps[20 + wid] = clock64();  // when each wave is done with its tasks
+        if (blockIdx.x == 0 && lane_c == 0 && it == A.n_iter - 1) g_stamps[20 + wid_c] = clock64();  // when each wave is done with its tasks
 #endif
         __syncthreads();
         LC_STAMP(15);
-        if (tid < SG * 5) {
-          const int sl = tid / 5, q = tid % 5;
+        if (tid_c < SG * 5) {
+          const int sl = tid_c / 5, q = tid_c % 5;
           if (g0 + sl < S && q != 2) {  // the x0 gradient (slot 2) comes out of the transposed row pass below
             float acc = 0.f;
             for (int k = 0; k < NBLK; ++k) acc += RED[((g0 + sl) * NBLK + k) * 5 + q];
@@ -931,7 +968,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       float dpre[NIT3][LC], wpre[NIT3][LC];
 #pragma unroll
       for (int i3 = 0; i3 < NIT3; ++i3) {
-        const int item0 = wid * 64 + i3 * NTHR, item = item0 + lane;
+        const int item0 = wid_c * 64 + i3 * NTHR, item = item0 + lane_c;
         const int sl = item0 / C::IPS_PAD, within = item % C::IPS_PAD, s = g0 + sl;
         const bool ok = (item0 < SG * C::IPS_PAD) && (s < S) && (within < C::IPS);
         const int jd = within % n, a0 = (within / n) * LC;
@@ -947,7 +984,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       {
         constexpr int WL = SS * (LR - 1) + NT;
         constexpr int NSTRIP = n / LR;
-        for (int item = tid; item < SG * N * NSTRIP; item += NTHR) {
+        for (int item = tid_c; item < SG * N * NSTRIP; item += NTHR) {
           const int u = item % N, strip = (item / N) % NSTRIP, sl = item / (N * NSTRIP);
           if (g0 + sl >= S) continue;
           const float *tx = TAPS + ((g0 + sl) * 4 + 0) * NTP;
@@ -982,9 +1019,9 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
         constexpr int NSTRIP = n / LC;
 #pragma unroll
         for (int i3 = 0; i3 < NIT3; ++i3) {
-          const int item0 = wid * 64 + i3 * NTHR;
+          const int item0 = wid_c * 64 + i3 * NTHR;
           if (item0 >= SG * C::IPS_PAD) break;
-          const int item = item0 + lane;
+          const int item = item0 + lane_c;
           const int sl = item0 / C::IPS_PAD;  // wave-uniform
           const int within = item % C::IPS_PAD;
           const int s = g0 + sl;
@@ -1031,7 +1068,8 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               gy = fmaf(rw, fy, gy);
               gs += rw;
               RES[(sl * n + id) * n + jd] = rw;
-              if (A.out_model) A.out_model[(size_t)f * S * n * n + pix] = model;
+              if constexpr (!LOOP_ONLY)
+                if (A.out_model) A.out_model[(size_t)f * S * n * n + pix] = model;
             }
             gy *= amp * SS;
           }
@@ -1040,7 +1078,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           gx = wave_sum(gx);
           gy = wave_sum(gy);
           gs = wave_sum(gs);
-          if (lane == 0) {
+          if (lane_c == 0) {
             float *r = RED + (sl * C::SLOTS + (item0 % C::IPS_PAD) / 64) * 5;
             r[0] = chi;
             r[1] = ga;
@@ -1053,8 +1091,8 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       __syncthreads();
       LC_STAMP(3 + 5 * (g0 / SG));
       // per-star sums in fixed slot order
-      if (tid < SG * 5) {
-        const int sl = tid / 5, q = tid % 5;
+      if (tid_c < SG * 5) {
+        const int sl = tid_c / 5, q = tid_c % 5;
         if (g0 + sl < S && q != 2) {  // the x0 gradient (slot 2) comes out of the transposed row pass (P5)
           float acc = 0.f;
           for (int k = 0; k < C::SLOTS; ++k) acc += RED[(sl * C::SLOTS + k) * 5 + q];
@@ -1065,7 +1103,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       {
         constexpr int WI = (SS * LA - 1 + NT - 1) / SS + 1;
         constexpr int NSTRIP = n / LA;
-        for (int item = tid; item < SG * n * NSTRIP; item += NTHR) {
+        for (int item = tid_c; item < SG * n * NSTRIP; item += NTHR) {
           const int jd = item % n, strip = (item / n) % NSTRIP, sl = item / (n * NSTRIP);
           if (g0 + sl >= S) continue;
           const float *ty = TAPS + ((g0 + sl) * 4 + 2) * NTP;
@@ -1142,7 +1180,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               gxs = fmaf(accp[p].y, tpix[p], gxs);
             }
             gxs = wave_sum(gxs);
-            if (lane == 0) REDX[s * C::NW + wid] = gxs;
+            if (lane_c == 0) REDX[s * C::NW + wid_c] = gxs;
           };
           auto nothing = [] {};
           // The request is made in two parts, each pinned where it stands (the scheduler otherwise sinks the reads behind the
@@ -1151,8 +1189,8 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           // would wait for the first of the reads they are meant to overlap.
           auto p5_window = [&](int sl, P5Ops &o, int bq) {
             o.amp = SP[(g0 + sl) * 4 + 0];
-            const float *vrow = V + (sl * N + pu) * C::VS + 1;
-            const int jd0 = bq + pv / SS;
+            const float *vrow = V + (sl * N + pu_c) * C::VS + 1;
+            const int jd0 = bq + pv_c / SS;
 #pragma unroll
             for (int i = 0; i < WJ; ++i) o.vwin[i] = vrow[min(max(jd0 + i, -1), n)];
             __builtin_amdgcn_sched_barrier(0);
@@ -1209,8 +1247,8 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
             lc_v2f accp[PX];
 #pragma unroll
             for (int p = 0; p < PX; ++p) accp[p] = (lc_v2f){0.f, 0.f};
-            const float *vrow = V + (sl * N + pu) * C::VS + 1;
-            const int jd0 = bq + pv / SS;
+            const float *vrow = V + (sl * N + pu_c) * C::VS + 1;
+            const int jd0 = bq + pv_c / SS;
             float vwin[WJ];
 #pragma unroll
             for (int i = 0; i < WJ; ++i) vwin[i] = vrow[min(max(jd0 + i, -1), n)];
@@ -1230,7 +1268,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               gxs = fmaf(accp[p].y, tpix[p], gxs);
             }
             gxs = wave_sum(gxs);
-            if (lane == 0) REDX[s * C::NW + wid] = gxs;
+            if (lane_c == 0) REDX[s * C::NW + wid_c] = gxs;
           }
         }
         __builtin_amdgcn_s_setprio(0);
@@ -1249,9 +1287,9 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           // (dotted with T, still in LDS), so that no second accumulator array is live
 #pragma unroll
           for (int i = 0; i < WJ; ++i) {
-            const int jd = i + bq + pv / SS;
+            const int jd = i + bq + pv_c / SS;
             const int ci = min(max(jd, 0), n - 1);
-            float vv = V[(sl * N + pu) * RS + ci];
+            float vv = V[(sl * N + pu_c) * RS + ci];
             vv = (jd >= 0 && jd < n) ? vv : 0.f;
             float dsum = 0.f;
 #pragma unroll
@@ -1259,7 +1297,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
               const int rel = SS * i - k;
               if (rel >= 0 && rel < PX) {
                 acc[rel] = fmaf(tx[k], vv, acc[rel]);
-                dsum = fmaf(dtx[k], T[pu * TS + pv + rel], dsum);
+                dsum = fmaf(dtx[k], T[pu_c * TS + pv_c + rel], dsum);
               }
             }
             gxs = fmaf(vv, dsum, gxs);
@@ -1267,7 +1305,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
 #pragma unroll
           for (int p = 0; p < PX; ++p) gB[p] = fmaf(amp, acc[p], gB[p]);
           gxs = wave_sum(gxs);
-          if (lane == 0) REDX[s * C::NW + wid] = gxs;
+          if (lane_c == 0) REDX[s * C::NW + wid_c] = gxs;
         }
       }
       LC_STAMP(17);
@@ -1289,10 +1327,10 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
           v.y = gB[4 * q + 1];
           v.z = gB[4 * q + 2];
           v.w = gB[4 * q + 3];
-          if (same_xcd) store_plain_x4(mine + pu * N + pv + 4 * q, v);
-          else store_sc1_x4(mine + pu * N + pv + 4 * q, v);
+          if (same_xcd) store_plain_x4(mine + pu_c * N + pv_c + 4 * q, v);
+          else store_sc1_x4(mine + pu_c * N + pv_c + 4 * q, v);
         }
-        if (tid == 0 && it == 0) store_sc1_f(mine + N * N + 1, __int_as_float(my_xcc + 1));
+        if (tid_c == 0 && it == 0) store_sc1_f(mine + N * N + 1, __int_as_float(my_xcc + 1));
       }
     }
     __syncthreads();  // (TRIM, role 0: the only barrier between P5 and the drain - REDX and SGR visible to the first wave)
@@ -1306,9 +1344,11 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       }
     }
 
-    if (A.out_gT) {
+    if constexpr (!LOOP_ONLY) {
+      if (A.out_gT) {
 #pragma unroll
-      for (int p = 0; p < PX; ++p) A.out_gT[gpix + p] = gB[p];
+        for (int p = 0; p < PX; ++p) A.out_gT[gpix + p] = gB[p];
+      }
     }
 
     // ---- P6: starlet l1 on B: value + sub-gradient (starlet_device.h) ---------------------------
@@ -1316,7 +1356,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     float z[PX];
 #pragma unroll
     for (int p = 0; p < PX; ++p) z[p] = 0.f;
-    if (starlet_role && (A.lam_sc != 0.f || A.lam_hf != 0.f)) {
+    if (starlet_role && (LOOP_ONLY || A.lam_sc != 0.f || A.lam_hf != 0.f)) {
       float bpix[PX];
       if (STATE_REGS) {
 #pragma unroll
@@ -1383,7 +1423,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       // (pixel state in registers only: at N = 128, where the update's traffic is two thirds of the tail, the C3 shard measured
       //  82.4 / 82.4 and 82.9, 83.3 / 82.6, 82.6 us per iteration with the late tables against without: the old order stays there)
       constexpr bool TAPS_LATE = STATE_REGS;
-      if (role == 0 && A.mode == 1) {
+      if (role == 0 && loop) {
         // (TRIM: no workgroup barrier between the x0 sums and the step any more; both are lanes of the first wave, 3 S <= 64)
         if constexpr (TRIM) wave_lds_sync();
         if (TAPS_LATE) step_stars(tid);
@@ -1424,7 +1464,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       }
       // role 0's tap tables of the next iteration, behind the barrier that follows the stars' step and beside the one lane's flag
       // round trip: the table entries go to the upper half of the workgroup first, whose waves do not wait for that lane
-      if (TAPS_LATE && role == 0 && A.mode == 1) compute_taps((tid + NTHR / 2) % NTHR);
+      if (TAPS_LATE && role == 0 && loop) compute_taps((tid + NTHR / 2) % NTHR);
       __syncthreads();
       LC_STAMP(46);
       if (*OK == 0) break;
@@ -1466,19 +1506,23 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       for (int s = 0; s < S; ++s) chi += SGR[s * 5];
       const float loss = 0.5f * chi + tl1;
       A.hist[(size_t)f * A.hist_stride + tglob] = loss;
-      if (A.out_loss) A.out_loss[f] = loss;
-      if (A.out_chi2) A.out_chi2[f] = chi;
+      if constexpr (!LOOP_ONLY) {
+        if (A.out_loss) A.out_loss[f] = loss;
+        if (A.out_chi2) A.out_chi2[f] = chi;
+      }
     }
-    if (A.out_ggrid) {
+    if constexpr (!LOOP_ONLY) {
+      if (A.out_ggrid) {
 #pragma unroll
-      for (int p = 0; p < PX; ++p) A.out_ggrid[gpix + p] = gB[p] + z[p];
-    }
-    if (A.out_gstars && tid < S * 4) {
-      const int s = tid / 4, q = tid % 4;
-      A.out_gstars[(size_t)f * S * 4 + tid] = SGR[s * 5 + 1 + q];
+        for (int p = 0; p < PX; ++p) A.out_ggrid[gpix + p] = gB[p] + z[p];
+      }
+      if (A.out_gstars && tid < S * 4) {
+        const int s = tid / 4, q = tid % 4;
+        A.out_gstars[(size_t)f * S * 4 + tid] = SGR[s * 5 + 1 + q];
+      }
     }
     // ---- AdaBelief update ---------------------------------------------------------------------
-    if (A.mode == 1) {
+    if (loop) {
       // no contraction here: which product of b1 * m + (1 - b1) * g gets fused is the compiler's choice per
       // instantiation, and the one- and two-workgroup forms of this kernel must produce the same bits
 #pragma clang fp contract(off)
@@ -1541,18 +1585,20 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
 #pragma unroll
         for (int p = 0; p < PX; ++p) {
           tpix_next[p] = Bp[p] + Tp[p];
-          T[pu * C::TSA + C::AP + pv + p] = tpix_next[p];
+          T[pu_c * C::TSA + C::AP + pv_c + p] = tpix_next[p];
         }
         // the loss, as in the other forms.  Its store is the lane's last instruction in front of the barrier: ahead of the
         // pixel step, the step's first wait on vmcnt (which the compiler places there for the state loaded in front of the
         // loop) would be a wait for this store.
-        if (tid == 0) {
+        if (tid_c == 0) {
           float chi = 0.f;
           for (int s = 0; s < S; ++s) chi += SGR[s * 5];
           const float loss = 0.5f * chi + tl1;
           A.hist[(size_t)f * A.hist_stride + tglob] = loss;
-          if (A.out_loss) A.out_loss[f] = loss;
-          if (A.out_chi2) A.out_chi2[f] = chi;
+          if constexpr (!LOOP_ONLY) {
+            if (A.out_loss) A.out_loss[f] = loss;
+            if (A.out_chi2) A.out_chi2[f] = chi;
+          }
         }
       }
     }
@@ -1560,7 +1606,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
     LC_STAMP(43);
   }  // iterations
 
-  if (A.mode == 1 && STATE_REGS && conv_role) {
+  if (loop && STATE_REGS && conv_role) {
     const size_t g0pix = (size_t)f * N * N + (size_t)(tid0 / (N / PX)) * N + (tid0 % (N / PX)) * PX;
 #pragma unroll
     for (int q = 0; q < PX / 4; ++q) {
@@ -1569,7 +1615,7 @@ __global__ __launch_bounds__(C::NTHR) void psf_fit_kernel(PsfArgs A) {
       ((float4 *)(A.sB + g0pix))[q] = make_float4(Sp_[4 * q], Sp_[4 * q + 1], Sp_[4 * q + 2], Sp_[4 * q + 3]);
     }
   }
-  if (A.mode == 1 && tid0 < S * 4 && conv_role) {
+  if (loop && tid0 < S * 4 && conv_role) {
     A.stars[(size_t)f * S * 4 + tid0] = SP[tid0];
     A.stars_m[(size_t)f * S * 4 + tid0] = SM[tid0];
     A.stars_s[(size_t)f * S * 4 + tid0] = SV[tid0];
